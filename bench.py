@@ -12,9 +12,21 @@ trains its own 128 clips and gradients are all-reduced over RCCL (weak scaling).
 is the configuration rounds 1-2 reported.  `--model vmae_video --neurons 512` runs C3 (ViT-Base,
 the reference plugin's own width).
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure needs:
+it sets up, warms up, times the N steps, writes its outputs if `--dump-outputs DIR` is given and
+prints the line; `roofline`, `cpu_baseline`, `parity`, `c3` and `c4` are null in it.  `--full` adds
+everything else listed below (each part still has its own `--no-*` / `--profile-steps 0` switch).
+
+`--dump-outputs DIR`: what the last timed step handed its caller, as float32 `DIR/<name>.npy`:
+`loss` (the step's return value), `losses` (every timed step's) and the trained state the step
+updates in place, one file per parameter tensor (`param_<name>`; a tensor past its share of the
+64 MB budget is cut to a fixed, seeded sample of its elements, in index order).  Model, clips and
+targets are seeded, so the same arguments give the same inputs in every run and build.
+
 Prints ONE JSON line (rank 0):
   * `value` = clips/s over EXACTLY `--steps` train steps, timers off, barrier + synchronize on
-    both sides, max over ranks;
+    both sides, max over ranks; `ms_per_step` = milliseconds per timed step;
+  * the rest needs `--full`:
   * `roofline`: a SEPARATE instrumented pass (`--profile-steps`, after the timed region) brackets
     every launch with hipEvents on its own launch stream (libvspike timers: one per kernel class,
     and one per Linear product of the ViT block — fwd / dX / dW of qkv, proj, fc1, fc2) and sums
@@ -65,7 +77,15 @@ def parse():
     ap.add_argument("--loss", default="poisson", choices=["poisson", "mse"], help="training.loss")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--profile-steps", type=int, default=10, help="instrumented steps after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the instrumented roofline pass, the CPU baseline, the full-batch "
+                         "parity check against the CPU oracle and the C3 / C4 sub-records (off: a plain run sets up, "
+                         "warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (its loss, every timed step's loss, "
+                         "the updated parameters) to DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--profile-steps", type=int, default=10,
+                    help="instrumented steps after the timed region (run under --full)")
     ap.add_argument("--batch", type=int, default=None,
                     help="clips per GPU (default: the train config's train_batch_size, 128 = the reference's)")
     ap.add_argument("--neurons", type=int, default=128)
@@ -445,10 +465,38 @@ def _barrier_sync(world):
     torch.cuda.synchronize()
 
 
+DUMP_BUDGET_BYTES = 56 << 20     # of float32 parameter samples; with the losses well under 64 MB in all
+
+
+def _dump_outputs(dump_dir, losses, model):
+    """`--dump-outputs`: what the last timed step handed its caller, as float32 .npy files: the loss it
+    returned (`loss`), every timed step's (`losses`), and the parameters it updated in place
+    (`param_<name>`, flat).  A tensor larger than its equal share of the budget is cut to a fixed
+    sample: indices drawn once from a CPU generator seeded with 0 (the same in every run and build),
+    sorted, so two dumps compare element by element."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    ls = torch.stack([x.detach().float().reshape(()) for x in losses]).cpu().numpy().astype(np.float32)
+    np.save(os.path.join(dump_dir, "loss.npy"), ls[-1:])
+    np.save(os.path.join(dump_dir, "losses.npy"), ls)
+    params = list(model.named_parameters())
+    share = max(1, DUMP_BUDGET_BYTES // 4 // max(1, len(params)))
+    for name, p in params:
+        flat = p.detach().reshape(-1)
+        if flat.numel() > share:
+            gen = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, flat.numel(), (share,), generator=gen).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(dump_dir, "param_" + name.replace(".", "_") + ".npy"),
+                flat.float().cpu().numpy().astype(np.float32))
+
+
 def _train_and_time(model, config, criterion, pixels, target, world, rank, dev, steps, warmup, profile_steps,
-                    graph=False, tag=""):
+                    graph=False, tag="", instrument=True, dump_dir=None):
     """W warm-up steps, EXACTLY `steps` timed steps between barrier + synchronize (max over ranks),
-    then the instrumented pass (per-kernel hipEvent timers, dW products in order)."""
+    then the instrumented pass (per-kernel hipEvent timers, dW products in order).  `instrument`
+    off skips that pass; the learning-rate schedule still spans `profile_steps`, so the timed steps
+    compute the same either way.  `dump_dir`: rank 0 writes the last timed step's outputs there."""
     from vspike import ops
     from vspike import _lib as L
     from vspike.dp import GradExchange
@@ -492,10 +540,12 @@ def _train_and_time(model, config, criterion, pixels, target, world, rank, dev, 
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)       # max and min over ranks agree iff all equal
         dist.all_reduce(lo, op=dist.ReduceOp.MAX)
         replicas_equal = bool(torch.equal(hi, -lo))
+    if dump_dir and rank == 0:
+        _dump_outputs(dump_dir, losses, model)
 
     # ---- instrumented pass (not part of `value`): every kernel class timed on its own stream
     kern = {}
-    if profile_steps > 0:
+    if instrument and profile_steps > 0:
         # side stream off for this pass: a weight-gradient product overlapped with the main stream's
         # kernels is timed from its launch to its end, including the time it waits for CUs that an
         # attention launch holds (2-3x its own duration); in order, every launch is timed alone
@@ -837,7 +887,7 @@ def main():
             "freeze": args.freeze, "lr": args.lr, "loss": args.loss, "batch": args.batch}
     config, criterion, model, B, pixels, target = _setup(spec, dev, rank)
     bb = model.backbone
-    do_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    do_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     parity = None
     L.dispatch_reset()
     if do_cpu:
@@ -853,7 +903,7 @@ def main():
         del out0, loss0
 
     run = _train_and_time(model, config, criterion, pixels, target, world, rank, dev, args.steps, args.warmup,
-                          args.profile_steps, graph=args.graph)
+                          args.profile_steps, graph=args.graph, instrument=args.full, dump_dir=args.dump_outputs)
     elapsed, final_loss, replicas_equal, dispatch = run["elapsed"], run["final_loss"], run["replicas_equal"], \
         run["dispatch"]
     redo = run["attn_redo_per_step"]
@@ -874,7 +924,7 @@ def main():
     c3 = None
     # the C3 / C4 sub-records are single-GPU evidence (N = 1 only): at N > 1 a rank that failed inside one
     # while the others sit in its collectives would hang the multi-GPU run the driver times
-    want_c3 = (not args.no_c3 and args.model == "vmae_tiny" and args.dtype == "bf16" and not args.graph and
+    want_c3 = (args.full and not args.no_c3 and args.model == "vmae_tiny" and args.dtype == "bf16" and not args.graph and
                not args.freeze and args.loss == "poisson" and world == 1)
     if want_c3:
         del run, model, pixels, target
@@ -888,7 +938,7 @@ def main():
             _progress(f"C3 sub-record failed: {c3['error']}")
 
     c4 = None
-    if not args.no_c4 and args.model == "vmae_tiny" and args.dtype == "bf16" and not args.graph and not args.freeze \
+    if args.full and not args.no_c4 and args.model == "vmae_tiny" and args.dtype == "bf16" and not args.graph and not args.freeze \
             and args.loss == "poisson" and world == 1:
         import gc
         gc.collect()
