@@ -497,6 +497,19 @@ int vs_avgpool3d(int64_t N, int64_t S, int64_t C, const float* x, float* pooled,
 int vs_avgpool3d_bwd(int64_t N, int64_t S, int64_t C, const float* dpool, float* dx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Token pool (csrc/token_pool.hip): the VideoMAE encoder's S tokens of each time step reduced to one
+ * token, the input of the temporal transformer stage.  G = clips * time steps.
+ * 16-byte accesses per lane; the summation order depends on S alone (bitwise reproducible, the same
+ * for a group computed alone or inside a batch).  Pointers 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+/* out[g][c] = (1/S) * sum_s x[(g*S+s)*ldx + c]  (+ pos[(g % pos_rows)*D + c] when pos != NULL);
+   out_lp (bf16, may be NULL) = out rounded to nearest-even. D % 64 == 0, ldx >= D, ldx % 4 == 0. */
+int vs_token_pool_fwd(int64_t G, int64_t S, int64_t D, const float* x, int64_t ldx, const float* pos,
+                      int64_t pos_rows, float* out, void* out_lp, void* stream);
+/* dx[(g*S+s)][c] = dpool[g][c] * (1/S) for every s; dx_lp (bf16, may be NULL) = dx rounded to nearest-even */
+int vs_token_pool_bwd(int64_t G, int64_t S, int64_t D, const float* dpool, float* dx, void* dx_lp, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Trial shards (host side of the input path; replaces the per-trial webdataset tars of
  * src/prepare_data.py:210-235 read by src/loader/base.py:21-41).  Fixed-size records: raw uint8
  * frames (T, C, H, W) + f32 spike counts (ap_rows, ap_cols) + a 64-byte "<eid>_<trial>" key.
@@ -529,7 +542,7 @@ const char* vs_shard_last_error(void);
 #define VS_TIMER_LN_FWD   4   /* vs_layernorm_fwd */
 #define VS_TIMER_LN_BWD   5   /* vs_layernorm_bwd (+ its partial-sum reduction) */
 #define VS_TIMER_ADAMW    6   /* vs_adamw */
-#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd) */
+#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd), vs_token_pool_fwd / _bwd */
 /* per-product tags of the ViT block executor (vs_vit_layer_fwd / _bwd): its vs_gemm calls are
    charged to these instead of VS_TIMER_GEMM / VS_TIMER_GEMM_DW, so every product has its own timer */
 #define VS_TIMER_FWD_QKV   8   /* qkv = h1 Wqkv^T + b          (mv:233-236) */
@@ -589,7 +602,8 @@ int vs_timing_bytes(int timer, double* algorithmic_bytes);   /* call before vs_t
 #define VS_PATH_CONV_DW      23   /* conv_dw_kernel: Conv3d weight gradient (implicit-GEMM gather, split over rows) */
 #define VS_PATH_GEMM_G256    24   /* gemm_bf16_g256_kernel: 256 x 256 persistent tiles, 64-deep LDS-DMA stages (long-M ViT-Base products) */
 #define VS_PATH_GEMM_DW256   25   /* gemm_dw256_kernel: long-K weight gradients on 256 x 256 persistent tiles + fixed-order reduce */
-#define VS_PATH_COUNT        26
+#define VS_PATH_TOKEN_POOL   26   /* vs_token_pool_fwd / vs_token_pool_bwd: one per call */
+#define VS_PATH_COUNT        27
 /* copies min(n, VS_PATH_COUNT) counters into out; returns VS_PATH_COUNT */
 int vs_dispatch_counts(int64_t* out, int n);
 int vs_dispatch_reset(void);

@@ -9,6 +9,7 @@ from .linear import Linear
 from .loss import MSEMeanLoss, PoissonNLLMeanLoss, make_criterion, mse_mean, poisson_nll_mean
 from .optim import FusedAdamW
 from .r3d import R3D
+from .temporal import VideoMAETemporal
 from .vit import VideoMAE
 
 NAME2MODEL = {
@@ -16,8 +17,10 @@ NAME2MODEL = {
     "VideoMAE": VideoMAE,
     # BASELINE C4's CNN encoder (no reference counterpart: SURVEY.md section 0), same plugin surface
     "R3D": R3D,
+    # BASELINE C5's encoder + temporal transformer stage (no reference counterpart either: DESIGN.md section 7)
+    "VideoMAETemporal": VideoMAETemporal,
 }
 
-__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "R3D", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
+__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
            "mse_mean", "MSEMeanLoss", "make_criterion",
            "DictConfig", "update_config", "config_from_kwargs", "load_run_config"]

@@ -3,7 +3,8 @@
 Replaces what the reference gets implicitly from `accelerator.prepare` -> torch DDP
 (src/train.py:61-64): an all-reduce(sum) of every trainable gradient per step, overlapped with
 the backward.  MI355X-first design:
-  * the VideoMAE plugin keeps its gradients in two flat f32 buffers; this class owns them
+  * the VideoMAE plugin keeps its gradients in two flat f32 buffers (VideoMAETemporal in three, its
+    temporal blocks' between the head's and the encoder's); this class owns them
     (`grad_buffer`) and the model reports finished ranges during its hand-sequenced backward
     (`mark_ready`) — head first (its 77 M-param Base gradient is ready before any encoder work),
     then encoder layers in reverse order;
@@ -60,7 +61,10 @@ class GradExchange:
             model.invalidate_lp()
         if hasattr(model, "grad_sink"):
             model.grad_sink = self
-            self._sunk = {id(model.enc_flat), id(model.head_flat)} if hasattr(model, "enc_flat") else set()
+            # the flat buffers whose gradients the model hands over through this sink (a plugin with
+            # more than the two names them in SUNK_BUFFERS): finish() leaves those to the buckets
+            names = getattr(model, "SUNK_BUFFERS", ("enc_flat", "head_flat"))
+            self._sunk = {id(getattr(model, n)) for n in names} if hasattr(model, "enc_flat") else set()
 
     def _mode(self) -> str:
         """'overlap' (launch bucketed all-reduces during the backward), 'local' (DDP no_sync

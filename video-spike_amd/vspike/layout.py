@@ -93,6 +93,32 @@ LAYER_KEYS = ("ln1_g", "ln1_b", "w_qkv", "b_qkv", "w_proj", "b_proj", "ln2_g", "
               "w_fc2", "b_fc2")
 
 
+def _layer_shapes(D: int, F: int):
+    """(key, shape) of one pre-LN block's parameters, in LAYER_KEYS order."""
+    return (("ln1_g", (D,)), ("ln1_b", (D,)), ("w_qkv", (3 * D, D)), ("b_qkv", (3 * D,)),
+            ("w_proj", (D, D)), ("b_proj", (D,)), ("ln2_g", (D,)), ("ln2_b", (D,)),
+            ("w_fc1", (F, D)), ("b_fc1", (F,)), ("w_fc2", (D, F)), ("b_fc2", (D,)))
+
+
+def _layer_hf_items(p: str, which: str, i: int, D: int):
+    """(hf_name, which_flat, slot_name, row_slice) of block i's parameters under the name prefix p."""
+    yield p + "attention.attention.query.weight", which, f"{i}.w_qkv", slice(0, D)
+    yield p + "attention.attention.key.weight", which, f"{i}.w_qkv", slice(D, 2 * D)
+    yield p + "attention.attention.value.weight", which, f"{i}.w_qkv", slice(2 * D, 3 * D)
+    yield p + "attention.attention.q_bias", which, f"{i}.b_qkv", slice(0, D)
+    yield p + "attention.attention.v_bias", which, f"{i}.b_qkv", slice(2 * D, 3 * D)
+    yield p + "attention.output.dense.weight", which, f"{i}.w_proj", None
+    yield p + "attention.output.dense.bias", which, f"{i}.b_proj", None
+    yield p + "intermediate.dense.weight", which, f"{i}.w_fc1", None
+    yield p + "intermediate.dense.bias", which, f"{i}.b_fc1", None
+    yield p + "output.dense.weight", which, f"{i}.w_fc2", None
+    yield p + "output.dense.bias", which, f"{i}.b_fc2", None
+    yield p + "layernorm_before.weight", which, f"{i}.ln1_g", None
+    yield p + "layernorm_before.bias", which, f"{i}.ln1_b", None
+    yield p + "layernorm_after.weight", which, f"{i}.ln2_g", None
+    yield p + "layernorm_after.bias", which, f"{i}.ln2_b", None
+
+
 class VitLayout:
     """encoder flat: patch_w, patch_b, then per layer LAYER_KEYS; head flat: enc_w, enc_b, dec_w, dec_b."""
 
@@ -105,9 +131,7 @@ class VitLayout:
         self.layer_ranges: List[Tuple[int, int]] = []
         for i in range(cfg.num_hidden_layers):
             lo = e.numel
-            for k, shape in (("ln1_g", (D,)), ("ln1_b", (D,)), ("w_qkv", (3 * D, D)), ("b_qkv", (3 * D,)),
-                             ("w_proj", (D, D)), ("b_proj", (D,)), ("ln2_g", (D,)), ("ln2_b", (D,)),
-                             ("w_fc1", (F, D)), ("b_fc1", (F,)), ("w_fc2", (D, F)), ("b_fc2", (D,))):
+            for k, shape in _layer_shapes(D, F):
                 e.add(f"{i}.{k}", shape)
             self.layer_ranges.append((lo, e.numel))
         self.enc = e
@@ -130,22 +154,47 @@ class VitLayout:
         yield "video_mae.embeddings.patch_embeddings.projection.weight", "enc", "patch_w", None
         yield "video_mae.embeddings.patch_embeddings.projection.bias", "enc", "patch_b", None
         for i in range(self.cfg.num_hidden_layers):
-            p = f"video_mae.encoder.layer.{i}."
-            yield p + "attention.attention.query.weight", "enc", f"{i}.w_qkv", slice(0, D)
-            yield p + "attention.attention.key.weight", "enc", f"{i}.w_qkv", slice(D, 2 * D)
-            yield p + "attention.attention.value.weight", "enc", f"{i}.w_qkv", slice(2 * D, 3 * D)
-            yield p + "attention.attention.q_bias", "enc", f"{i}.b_qkv", slice(0, D)
-            yield p + "attention.attention.v_bias", "enc", f"{i}.b_qkv", slice(2 * D, 3 * D)
-            yield p + "attention.output.dense.weight", "enc", f"{i}.w_proj", None
-            yield p + "attention.output.dense.bias", "enc", f"{i}.b_proj", None
-            yield p + "intermediate.dense.weight", "enc", f"{i}.w_fc1", None
-            yield p + "intermediate.dense.bias", "enc", f"{i}.b_fc1", None
-            yield p + "output.dense.weight", "enc", f"{i}.w_fc2", None
-            yield p + "output.dense.bias", "enc", f"{i}.b_fc2", None
-            yield p + "layernorm_before.weight", "enc", f"{i}.ln1_g", None
-            yield p + "layernorm_before.bias", "enc", f"{i}.ln1_b", None
-            yield p + "layernorm_after.weight", "enc", f"{i}.ln2_g", None
-            yield p + "layernorm_after.bias", "enc", f"{i}.ln2_b", None
+            yield from _layer_hf_items(f"video_mae.encoder.layer.{i}.", "enc", i, D)
+        yield "encoder.weight", "head", "enc_w", None
+        yield "encoder.bias", "head", "enc_b", None
+        yield "decoder.weight", "head", "dec_w", None
+        yield "decoder.bias", "head", "dec_b", None
+
+
+class TemporalLayout(VitLayout):
+    """VideoMAETemporal: the encoder flat of VitLayout unchanged; a third flat `temp` with the temporal
+    blocks (LAYER_KEYS per layer, MLP width `temporal_mlp`); the head's first Linear reads the
+    T' = num_frames / tubelet_size pooled tokens, enc_w (enc_out, T' * D)."""
+
+    def __init__(self, cfg: BackboneCfg, enc_out: int, out_dim: int, temporal_layers: int, temporal_mlp: int):
+        super().__init__(cfg, enc_out, out_dim)
+        self.temporal_layers, self.temporal_mlp = temporal_layers, temporal_mlp
+        self.time_steps = cfg.num_frames // cfg.tubelet_size
+        D = cfg.hidden_size
+        t = FlatLayout()
+        self.temp_ranges: List[Tuple[int, int]] = []
+        for j in range(temporal_layers):
+            lo = t.numel
+            for k, shape in _layer_shapes(D, temporal_mlp):
+                t.add(f"{j}.{k}", shape)
+            self.temp_ranges.append((lo, t.numel))
+        self.temp = t
+        h = FlatLayout()
+        h.add("enc_w", (enc_out, self.time_steps * D))
+        h.add("enc_b", (enc_out,))
+        h.add("dec_w", (out_dim, enc_out))
+        h.add("dec_b", (out_dim,))
+        self.head = h
+
+    def hf_items(self):
+        """The encoder's names unchanged, then `temporal.layer.{j}.` + the sub-names of an encoder layer
+        (flat "temp"), then the head."""
+        D = self.cfg.hidden_size
+        for item in super().hf_items():
+            if item[1] == "enc":
+                yield item
+        for j in range(self.temporal_layers):
+            yield from _layer_hf_items(f"temporal.layer.{j}.", "temp", j, D)
         yield "encoder.weight", "head", "enc_w", None
         yield "encoder.bias", "head", "enc_b", None
         yield "decoder.weight", "head", "dec_w", None

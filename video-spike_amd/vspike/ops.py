@@ -312,6 +312,30 @@ def cast(x, out):
     return out
 
 
+def token_pool_fwd(x, S, out, pos=None, out_lp=None):
+    """out[g] = mean of the S consecutive rows g*S .. g*S+S-1 of x [G*S, D] f32 (row stride x.stride(0))
+    (+ pos[g % pos.shape[0]]); out_lp (optional bf16 [G, D]) = out rounded (vs_token_pool_fwd)."""
+    require_device(x, out, pos, out_lp)
+    G, D = out.shape
+    if x.shape[0] != G * S or x.shape[1] != D or (pos is not None and pos.shape[1] != D):
+        raise L.VsError("token_pool_fwd: x must be [G*S, D], out [G, D], pos [rows, D]")
+    check(lib().vs_token_pool_fwd(G, S, D, x.data_ptr(), x.stride(0), ptr(pos), pos.shape[0] if pos is not None else 0,
+                                  out.data_ptr(), ptr(out_lp), stream()), "vs_token_pool_fwd")
+    return out
+
+
+def token_pool_bwd(dpool, S, dx, dx_lp=None):
+    """dx[g*S + s] = dpool[g] / S for every s (dx [G*S, D] f32, dense); dx_lp (optional bf16) = dx
+    rounded (vs_token_pool_bwd)."""
+    require_device(dpool, dx, dx_lp)
+    G, D = dpool.shape
+    if dx.numel() != G * S * D or (dx_lp is not None and dx_lp.numel() != G * S * D):
+        raise L.VsError("token_pool_bwd: dx (and dx_lp) must hold G*S rows of D")
+    check(lib().vs_token_pool_bwd(G, S, D, dpool.data_ptr(), dx.data_ptr(), ptr(dx_lp), stream()),
+          "vs_token_pool_bwd")
+    return dx
+
+
 def poisson_nll(log_rate, target, loss_out, dx=None, grad_scale=1.0, workspace=None):
     require_device(log_rate, target, loss_out)
     n = log_rate.numel()

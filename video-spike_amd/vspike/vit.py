@@ -96,7 +96,7 @@ class VideoMAE(nn.Module):
         if self.fp8 and (cfg.hidden_size % 128 or cfg.intermediate_size % 128):
             raise ValueError("compute_dtype fp8 (MX-FP8 block products) needs hidden_size and intermediate_size "
                              "multiples of 128 (e.g. videomae-base)")
-        self.layout = VitLayout(cfg, enc_out, out_dim)
+        self.layout = self._make_layout(config, enc_out, out_dim)
         self.enc_flat = nn.Parameter(torch.zeros(self.layout.enc.numel), requires_grad=not self.freeze_encoder)
         self.head_flat = nn.Parameter(torch.zeros(self.layout.head.numel))
         # raw-video path (videomae.py:10-11, 18-25): uniform num_frames-of-T frame selection, then
@@ -112,6 +112,9 @@ class VideoMAE(nn.Module):
         self.grad_sink = None          # set by vspike.dp.GradExchange for overlapped all-reduce
         self._pos_cache = {}
         self.reset_parameters()
+
+    def _make_layout(self, config, enc_out: int, out_dim: int):
+        return VitLayout(self.backbone, enc_out, out_dim)
 
     # ---------------------------------------------------------------------------------------
     # parameters
@@ -137,6 +140,10 @@ class VideoMAE(nn.Module):
 
     def _flat(self, which):
         return self.enc_flat if which == "enc" else self.head_flat
+
+    def _flat_params(self):
+        """(short name, flat f32 parameter buffer) of every buffer that has a bf16 shadow."""
+        return (("enc", self.enc_flat), ("head", self.head_flat))
 
     def _flat_layout(self, which):
         return self.layout.enc if which == "enc" else self.layout.head
@@ -208,6 +215,9 @@ class VideoMAE(nn.Module):
             with torch.no_grad():
                 inputs = self.preprocess(inputs.detach())
         pixels = inputs.detach().to(torch.float32).contiguous()
+        return self._apply_fn(pixels)
+
+    def _apply_fn(self, pixels):
         return _VideoMAEFn.apply(pixels, self.enc_flat, self.head_flat, self)
 
     def _pos_table(self, device):
@@ -291,7 +301,7 @@ class VideoMAE(nn.Module):
         if key not in sh:
             dt = self.compute_dtype
             ent = {}
-            for name, p in (("enc", self.enc_flat), ("head", self.head_flat)):
+            for name, p in self._flat_params():
                 t = torch.empty(p.numel(), dtype=dt, device=dev)
                 stamp = {}
                 register_lp_shadow(p, t, stamp)
@@ -331,10 +341,36 @@ class VideoMAE(nn.Module):
         if ent is not None and ent["sig"] == sig and (ent["owner"] is None or ent["owner"]() is None):
             return ent
         cfg, dt = self.backbone, self.compute_dtype
-        N, D, Lyr = cfg.num_tokens, cfg.hidden_size, cfg.num_hidden_layers
-        M = B * N
+        N, D = cfg.num_tokens, cfg.hidden_size
         lp = dt != torch.float32
         ar = Arena()
+        fused = self._plan_encoder(ar, B, save_encoder)
+        if lp:
+            ar.add("x_lp", (B, N * D), dt)
+        ar.add("z", (B, self.layout.enc_out), torch.float32)
+        # split-K over the N*D = 301,056-long reduction; partials summed in order (deterministic)
+        hws = ops.splitk_workspace_bytes(dt, B, self.layout.enc_out, N * D)
+        if hws:
+            ar.add("head_ws", (hws // 4 + 4,), torch.float32)
+        act = ar.allocate(dev)
+        if lp:
+            enc_lp, head_lp = self._lp_shadows(dev)["enc"][0], self._lp_shadows(dev)["head"][0]
+        else:
+            enc_lp, head_lp = enc32, head32
+        structs, x = self._encoder_structs(act, B, save_encoder, enc_lp, enc32)
+        new = {"act": act, "structs": structs, "enc_lp": enc_lp, "head_lp": head_lp, "x_final": x, "fused": fused,
+               "x_flat_lp": act["x_lp"] if lp else x.view(B, N * D), "head_ws": act.get("head_ws"),
+               "sig": sig, "owner": None}
+        if ent is None or ent["sig"] != sig:
+            fwd_cache[key] = new
+        return new
+
+    def _plan_encoder(self, ar: Arena, B: int, save_encoder: bool) -> bool:
+        """Plan the encoder's activation buffers of one forward; returns whether the patch embedding
+        runs the fused gather GEMM."""
+        cfg, dt = self.backbone, self.compute_dtype
+        N, D, Lyr = cfg.num_tokens, cfg.hidden_size, cfg.num_hidden_layers
+        M = B * N
         # patch embedding: the fused gather GEMM (49.9 us vs 61.8 us for im2col + GEMM at C2,
         # profiles/r03_v2_microbench_patch.txt); when the encoder trains, its weight gradient gathers
         # the pixels again in its own operand load (vs_patch_embed_dw), so no cols tensor exists in
@@ -351,18 +387,12 @@ class VideoMAE(nn.Module):
             ar.add("fp8_ws", (int(L.lib().vs_vit_fp8_workspace_bytes(M, D, cfg.intermediate_size)),), torch.uint8)
         for j in range(Lyr if save_encoder else 2):
             ar.add(f"X{j}", (M, D), torch.float32)
-        if lp:
-            ar.add("x_lp", (B, N * D), dt)
-        ar.add("z", (B, self.layout.enc_out), torch.float32)
-        # split-K over the N*D = 301,056-long reduction; partials summed in order (deterministic)
-        hws = ops.splitk_workspace_bytes(dt, B, self.layout.enc_out, N * D)
-        if hws:
-            ar.add("head_ws", (hws // 4 + 4,), torch.float32)
-        act = ar.allocate(dev)
-        if lp:
-            enc_lp, head_lp = self._lp_shadows(dev)["enc"][0], self._lp_shadows(dev)["head"][0]
-        else:
-            enc_lp, head_lp = enc32, head32
+        return fused
+
+    def _encoder_structs(self, act, B: int, save_encoder: bool, enc_lp, enc32):
+        """The block executor structs over planned buffers; returns (structs, the last block's output)."""
+        cfg = self.backbone
+        Lyr = cfg.num_hidden_layers
         x = act["x0"]
         structs = []
         for i in range(Lyr):
@@ -378,40 +408,46 @@ class VideoMAE(nn.Module):
                 s.next_ln_g, s.next_ln_b = lay.view(enc32, f"{i + 1}.ln1_g").data_ptr(), lay.view(enc32, f"{i + 1}.ln1_b").data_ptr()
                 s.next_h1, s.next_mean1, s.next_rstd1 = t.h1, t.mean1, t.rstd1
                 t.ln1_ready = 1
-        new = {"act": act, "structs": structs, "enc_lp": enc_lp, "head_lp": head_lp, "x_final": x, "fused": fused,
-               "x_flat_lp": act["x_lp"] if lp else x.view(B, N * D), "head_ws": act.get("head_ws"),
-               "sig": sig, "owner": None}
-        if ent is None or ent["sig"] != sig:
-            fwd_cache[key] = new
-        return new
+        return structs, x
 
-    def _run_forward(self, pixels, save_encoder: bool):
-        cfg, dt = self.backbone, self.compute_dtype
-        B = pixels.shape[0]
-        N, D = cfg.num_tokens, cfg.hidden_size
+    def _refresh_lp(self, dev):
+        """bf16 shadows: FusedAdamW rewrites them with each update (vs_adamw param_lp); cast only
+        when the master weights changed some other way (load, init, a user's in-place write)."""
+        if self.compute_dtype == torch.float32:
+            return
+        sh = self._lp_shadows(dev)
+        for name, p in self._flat_params():
+            shadow, stamp = sh[name]
+            if p.numel() and stamp.get("key") != lp_key(p):
+                ops.cast(p.detach(), shadow)
+                stamp["key"] = lp_key(p)
+
+    def _encoder_forward(self, ent, pixels):
+        """Patch embedding (+ the sinusoid table) and the encoder blocks into ent["x_final"]."""
+        cfg = self.backbone
         dev = pixels.device
-        enc32, head32 = self.enc_flat.detach(), self.head_flat.detach()
-        le, lh = self.layout.enc, self.layout.head
-        ent = self._fwd_buffers(B, dev, save_encoder)
-        act, enc_lp, head_lp = ent["act"], ent["enc_lp"], ent["head_lp"]
-        if dt != torch.float32:
-            # bf16 shadows: FusedAdamW rewrites them with each update (vs_adamw param_lp); cast only
-            # when the master weights changed some other way (load, init, a user's in-place write)
-            sh = self._lp_shadows(dev)
-            for p, (shadow, stamp) in ((self.enc_flat, sh["enc"]), (self.head_flat, sh["head"])):
-                if stamp.get("key") != lp_key(p):
-                    ops.cast(p.detach(), shadow)
-                    stamp["key"] = lp_key(p)
-
+        act, enc_lp, enc32, le = ent["act"], ent["enc_lp"], self.enc_flat.detach(), self.layout.enc
         if ent["fused"]:   # tubelet gather inside the GEMM's operand load (no im2col pass)
             ops.patch_embed_fwd(pixels, le.view(enc_lp, "patch_w"), le.view(enc32, "patch_b"), self._pos_table(dev),
                                 act["x0"], cfg.tubelet_size, cfg.patch_size, cols=act.get("cols"))
         else:
             ops.patch_im2col(pixels, act["cols"], cfg.tubelet_size, cfg.patch_size)
             ops.linear(act["cols"], le.view(enc_lp, "patch_w"), act["x0"], bias=le.view(enc32, "patch_b"),
-                       epilogue=L.EPI_POS, pos=self._pos_table(dev), pos_rows=N)
+                       epilogue=L.EPI_POS, pos=self._pos_table(dev), pos_rows=cfg.num_tokens)
         for s in ent["structs"]:
             ops.vit_layer_fwd(s)
+
+    def _run_forward(self, pixels, save_encoder: bool):
+        cfg, dt = self.backbone, self.compute_dtype
+        B = pixels.shape[0]
+        N, D = cfg.num_tokens, cfg.hidden_size
+        dev = pixels.device
+        head32 = self.head_flat.detach()
+        lh = self.layout.head
+        ent = self._fwd_buffers(B, dev, save_encoder)
+        act, enc_lp, head_lp = ent["act"], ent["enc_lp"], ent["head_lp"]
+        self._refresh_lp(dev)
+        self._encoder_forward(ent, pixels)
         x_flat_lp = ent["x_flat_lp"]
         if dt != torch.float32:
             ops.cast(ent["x_final"].view(B, N * D), x_flat_lp)
@@ -440,20 +476,15 @@ class VideoMAE(nn.Module):
         if self.grad_sink is not None:
             self.grad_sink.mark_ready(p, lo, hi)
 
-    def _run_backward(self, st, d_logrates, want_enc: bool, want_head: bool):
+    def _bwd_scratch(self, B: int, dev):
+        """Backward scratch of one (batch, device) shape, and its cache key."""
         cfg, dt = self.backbone, self.compute_dtype
-        B = st["B"]
-        N, D, F, Lyr = cfg.num_tokens, cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
+        N, D, F = cfg.num_tokens, cfg.hidden_size, cfg.intermediate_size
         H = cfg.num_attention_heads
         M = B * N
-        lay, le, lh = self.layout, self.layout.enc, self.layout.head
-        act = st["act"]
-        dev = d_logrates.device
-        head32 = self.head_flat.detach()
-        dr = d_logrates.reshape(B, lay.out_dim).to(torch.float32).contiguous()
-
+        lay = self.layout
         lp = dt != torch.float32
-        _, bwd_cache, gs_cache = self._caches()
+        _, bwd_cache, _ = self._caches()
         bkey = (B, _dev_key(dev), dt)
         g = bwd_cache.get(bkey)
         if g is None:
@@ -480,6 +511,20 @@ class VideoMAE(nn.Module):
             ar.add("gemm_ws", (gws // 4 + 64,), torch.float32)
             g = ar.allocate(dev)
             bwd_cache[bkey] = g
+        return g, bkey
+
+    def _run_backward(self, st, d_logrates, want_enc: bool, want_head: bool):
+        dt = self.compute_dtype
+        B = st["B"]
+        N, D = self.backbone.num_tokens, self.backbone.hidden_size
+        lay, lh = self.layout, self.layout.head
+        act = st["act"]
+        dev = d_logrates.device
+        head32 = self.head_flat.detach()
+        dr = d_logrates.reshape(B, lay.out_dim).to(torch.float32).contiguous()
+
+        lp = dt != torch.float32
+        g, bkey = self._bwd_scratch(B, dev)
 
         g_head = self._grad_buffer(self.head_flat) if want_head else None
         Gh = lambda n: lh.view(g_head, n)  # noqa: E731
@@ -504,12 +549,26 @@ class VideoMAE(nn.Module):
             return None, g_head
 
         g_enc = self._grad_buffer(self.enc_flat)
-        Ge = lambda n: le.view(g_enc, n)  # noqa: E731
-
         dx, dx_lp = g["dxA"], (g["dxA_lp"] if lp else None)
         ops.linear_dx(dz_lp, lh.view(st["head_lp"], "enc_w"), dx.view(B, N * D))
         if lp:
             ops.cast(dx, dx_lp)
+        self._encoder_backward(st, g, bkey, g_enc)
+        return g_enc, g_head
+
+    def _encoder_backward(self, st, g, bkey, g_enc):
+        """The encoder blocks in reverse and the patch embedding, from the gradient of the encoder
+        output in g["dxA"] (and its bf16 copy g["dxA_lp"]); weight gradients go into g_enc."""
+        cfg, dt = self.backbone, self.compute_dtype
+        B = st["B"]
+        N, Lyr = cfg.num_tokens, cfg.num_hidden_layers
+        lay, le = self.layout, self.layout.enc
+        act = st["act"]
+        dev = g_enc.device
+        lp = dt != torch.float32
+        gs_cache = self._caches()[2]
+        Ge = lambda n: le.view(g_enc, n)  # noqa: E731
+        dx, dx_lp = g["dxA"], (g["dxA_lp"] if lp else None)
         gkey = (bkey, g_enc.data_ptr())
         grads = gs_cache.get(gkey)
         if grads is None:
@@ -566,7 +625,6 @@ class VideoMAE(nn.Module):
         else:
             ops.linear_dw(dx, act["cols"], Ge("patch_w"), db=Ge("patch_b"))
         self._ready(self.enc_flat, 0, lay.layer_ranges[0][0] if lay.layer_ranges else self.enc_flat.numel())
-        return g_enc, g_head
 
 
 class _VideoMAEFn(torch.autograd.Function):
