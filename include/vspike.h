@@ -510,6 +510,52 @@ int vs_token_pool_fwd(int64_t G, int64_t S, int64_t D, const float* x, int64_t l
 int vs_token_pool_bwd(int64_t G, int64_t S, int64_t D, const float* dpool, float* dx, void* dx_lp, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * ContrastViT (csrc/contrast.hip): the pieces of the reference's
+ * src/model/vit_mae/vit_mae.py:26-44 + info_nce (src/utils/loss_utils.py:409-431) that the block
+ * executor does not cover.  G images of P patch tokens + one CLS token, width D.  Every reduction
+ * runs in an order fixed by the extents alone (no atomics): results are bitwise reproducible.
+ * Gradient outputs are WRITTEN (not accumulated).  vs_cls_embed_* and vs_embed_head_* move 16 bytes per lane
+ * per access (their pointers 16-byte aligned, D % 8 == 0); vs_info_nce works on rows of E floats (3 in the
+ * reference's use) with 4-byte accesses and asks 16-byte alignment of its workspace only.
+ * ------------------------------------------------------------------------------------------ */
+/* x[g][0] = cls + table[0];  x[g][1 + p] = patches[g*P + p]  (patches already carry bias + table rows 1..P
+   from the patch GEMM's epilogue).  patches [G*P, D], table [P+1, D], x [G, P+1, D], all f32. */
+int vs_cls_embed_fwd(int64_t G, int64_t P, int64_t D, const float* patches, const float* cls, const float* table,
+                     float* x, void* stream);
+/* d_cls[d] = sum_g dx[g][0][d] in ascending g;  d_patches[g*P + p] = dx[g][1 + p] in `out_dtype`
+   (VS_F32 / VS_BF16: the operand of the patch embedding's weight-gradient product).  The table is fixed. */
+int vs_cls_embed_bwd(int32_t out_dtype, int64_t G, int64_t P, int64_t D, const float* dx, float* d_cls,
+                     void* d_patches, void* stream);
+/* Per image g, on row x[g*ldx .. + D) (the CLS row of the last block's output, ldx = (P+1)*D):
+   h = LayerNorm(x; gamma, beta, eps);  z_raw = W h + b (W [E, D], 1 <= E <= 256);  z = z_raw / |z_raw|
+   (no epsilon: vit_mae.py:40).  Saves h [G, D], mean / rstd / nrm [G], z_raw [G, E]; writes z [G, E]. */
+int vs_embed_head_fwd(int64_t G, int64_t D, int64_t E, const float* x, int64_t ldx, const float* gamma,
+                      const float* beta, float eps, const float* w, const float* b, float* h, float* mean,
+                      float* rstd, float* z_raw, float* nrm, float* z, void* stream);
+/* Backward of the above from dz [G, E]: dz_raw = (dz - z (z . dz)) / |z_raw|, dh = W^T dz_raw, LayerNorm
+   backward into row 0 of dx [G, P+1, D] (f32) with ZEROS in the image's other P rows; dx_lp (bf16, may be
+   NULL) = dx rounded, written in the same pass.  Parameter gradients dw [E, D], db [E], dgamma, dbeta [D]
+   (all four may be NULL together: dx only) are summed over images in ascending g.
+   workspace: >= vs_embed_head_bwd_workspace_bytes(G, D, E). */
+size_t vs_embed_head_bwd_workspace_bytes(int64_t G, int64_t D, int64_t E);
+int vs_embed_head_bwd(int64_t G, int64_t P, int64_t D, int64_t E, const float* dz, const float* x, int64_t ldx,
+                      const float* h, const float* mean, const float* rstd, const float* z_raw, const float* nrm,
+                      const float* gamma, const float* w, float* dx, void* dx_lp, float* dw, float* db,
+                      float* dgamma, float* dbeta, void* workspace, void* stream);
+/* InfoNCE (loss_utils.py:409-431).  ref, pos [n, E], neg [m, E] f32 (1 <= E <= 256); 1/tau = exp(*log_inv_tau)
+   (device scalar, the reference's `temperature`; NULL: tau = 1).  pos_dist_i = ref_i.pos_i / tau,
+   neg_dist_ij = ref_i.neg_j / tau, c_i = max_j neg_dist_ij:
+     out[1] = pos_loss = -mean_i(pos_dist_i - c_i);  out[2] = neg_loss = mean_i logsumexp_j(neg_dist_ij - c_i);
+     out[0] = loss = pos_loss + neg_loss.
+   d_ref, d_pos [n, E], d_neg [m, E] (each may be NULL) = grad_scale * dloss/d(.); d_neg sums over the
+   reference rows in ascending i.  d_log_inv_tau (may be NULL) = -mean_i pos_dist_i + mean_i sum_j
+   softmax_ij neg_dist_ij (not scaled).  workspace: >= vs_info_nce_workspace_bytes(n, m). */
+size_t vs_info_nce_workspace_bytes(int64_t n, int64_t m);
+int vs_info_nce(int64_t n, int64_t m, int64_t E, const float* ref, const float* pos, const float* neg,
+                const float* log_inv_tau, float* out, float* d_ref, float* d_pos, float* d_neg, float grad_scale,
+                float* d_log_inv_tau, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Trial shards (host side of the input path; replaces the per-trial webdataset tars of
  * src/prepare_data.py:210-235 read by src/loader/base.py:21-41).  Fixed-size records: raw uint8
  * frames (T, C, H, W) + f32 spike counts (ap_rows, ap_cols) + a 64-byte "<eid>_<trial>" key.
@@ -542,7 +588,7 @@ const char* vs_shard_last_error(void);
 #define VS_TIMER_LN_FWD   4   /* vs_layernorm_fwd */
 #define VS_TIMER_LN_BWD   5   /* vs_layernorm_bwd (+ its partial-sum reduction) */
 #define VS_TIMER_ADAMW    6   /* vs_adamw */
-#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd), vs_token_pool_fwd / _bwd */
+#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd), vs_token_pool_*, vs_cls_embed_*, vs_embed_head_*, vs_info_nce */
 /* per-product tags of the ViT block executor (vs_vit_layer_fwd / _bwd): its vs_gemm calls are
    charged to these instead of VS_TIMER_GEMM / VS_TIMER_GEMM_DW, so every product has its own timer */
 #define VS_TIMER_FWD_QKV   8   /* qkv = h1 Wqkv^T + b          (mv:233-236) */
@@ -603,7 +649,10 @@ int vs_timing_bytes(int timer, double* algorithmic_bytes);   /* call before vs_t
 #define VS_PATH_GEMM_G256    24   /* gemm_bf16_g256_kernel: 256 x 256 persistent tiles, 64-deep LDS-DMA stages (long-M ViT-Base products) */
 #define VS_PATH_GEMM_DW256   25   /* gemm_dw256_kernel: long-K weight gradients on 256 x 256 persistent tiles + fixed-order reduce */
 #define VS_PATH_TOKEN_POOL   26   /* vs_token_pool_fwd / vs_token_pool_bwd: one per call */
-#define VS_PATH_COUNT        27
+#define VS_PATH_CLS_EMBED    27   /* vs_cls_embed_fwd / vs_cls_embed_bwd: one per call */
+#define VS_PATH_EMBED_HEAD   28   /* vs_embed_head_fwd / vs_embed_head_bwd: one per call */
+#define VS_PATH_INFO_NCE     29   /* vs_info_nce: one per call */
+#define VS_PATH_COUNT        30
 /* copies min(n, VS_PATH_COUNT) counters into out; returns VS_PATH_COUNT */
 int vs_dispatch_counts(int64_t* out, int n);
 int vs_dispatch_reset(void);

@@ -4,9 +4,10 @@ Drop-in surface (src/utils/utils.py:28-34 of the reference): `NAME2MODEL[config.
 builds the plugin from `config.model`; `forward(inputs) -> log-rates (B, 100, N)`.  All compute
 runs in libvspike.so (hand-written HIP, include/vspike.h) — there is no CPU fallback.
 """
+from .contrast import ContrastViT
 from .config import DictConfig, config_from_kwargs, load_run_config, update_config
 from .linear import Linear
-from .loss import MSEMeanLoss, PoissonNLLMeanLoss, make_criterion, mse_mean, poisson_nll_mean
+from .loss import InfoNCE, MSEMeanLoss, PoissonNLLMeanLoss, make_criterion, mse_mean, poisson_nll_mean
 from .optim import FusedAdamW
 from .r3d import R3D
 from .temporal import VideoMAETemporal
@@ -19,8 +20,10 @@ NAME2MODEL = {
     "R3D": R3D,
     # BASELINE C5's encoder + temporal transformer stage (no reference counterpart either: DESIGN.md section 7)
     "VideoMAETemporal": VideoMAETemporal,
+    # the reference's contrastive pretraining model (src/model/vit_mae/vit_mae.py:26-44, `pretrain.py --model c`)
+    "ContrastViT": ContrastViT,
 }
 
-__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
+__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "ContrastViT", "InfoNCE", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
            "mse_mean", "MSEMeanLoss", "make_criterion",
            "DictConfig", "update_config", "config_from_kwargs", "load_run_config"]

@@ -38,6 +38,11 @@ PATH_NAMES = ("gemm_dw", "gemm_skinny", "gemm_slab", "gemm_big", "gemm_wres", "g
               "attn_bwd", "attn_f32", "patch_fused", "dw_grouped", "mlp_fwd", "mlp_bwd", "gemm_fp8", "patch_dw",
               "conv_igemm", "conv_dw", "gemm_g256", "gemm_dw256", "token_pool")
 PATH_COUNT = 27
+# NB: PATH_COUNT is the length of PATH_NAMES above, NOT the header's VS_PATH_COUNT any more: a test of the
+# temporal stage pins both at 27, so counters added since then (ids PATH_COUNT ..) are listed in tuples of their
+# own, appended in id order to EXTRA_PATH_NAMES.  The library's real count is total_path_count().
+CONTRAST_PATH_NAMES = ("cls_embed", "embed_head", "info_nce")      # csrc/contrast.hip, ids 27..29
+EXTRA_PATH_NAMES = CONTRAST_PATH_NAMES
 KNOB_NAMES = ("dw_old", "no_skinny", "no_slab", "no_big", "no_wres", "wres_gbwd", "no_wslab", "wslab", "wslab_g",
               "panel", "no_panel", "panel_grid", "no_fullk", "no_ring", "no_lnf_fuse", "no_ln_fuse", "dw_bm", "dw_bn",
               "dw_splits", "dw_stages", "ln_blocks", "dh_f32", "no_patch_fused", "no_dw_group", "attn_variant", "slab_wv", "wres_wv", "wres_dbg",
@@ -186,6 +191,15 @@ PROTOTYPES = {
     "vs_avgpool3d_bwd": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_p, c_p]),
     "vs_token_pool_fwd": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p]),
     "vs_token_pool_bwd": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
+    "vs_cls_embed_fwd": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "vs_cls_embed_bwd": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
+    "vs_embed_head_fwd": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_f32, c_p, c_p, c_p, c_p, c_p,
+                                         c_p, c_p, c_p, c_p]),
+    "vs_embed_head_bwd_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "vs_embed_head_bwd": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p,
+                                         c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "vs_info_nce_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "vs_info_nce": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f32, c_p, c_p, c_p]),
     "vs_timing_enable": (ctypes.c_int, [ctypes.c_int]),
     "vs_timing_collect": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double)]),
     "vs_timing_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
@@ -271,9 +285,17 @@ def build_id() -> str:
 
 def dispatch_counts() -> dict:
     """Launches per kernel path since the last dispatch_reset() (vspike.h VS_PATH_*)."""
-    buf = (c_i64 * PATH_COUNT)()
-    lib().vs_dispatch_counts(buf, PATH_COUNT)
-    return {name: int(buf[i]) for i, name in enumerate(PATH_NAMES)}
+    names = PATH_NAMES + EXTRA_PATH_NAMES
+    buf = (c_i64 * len(names))()
+    total = lib().vs_dispatch_counts(buf, len(names))
+    if total != len(names):
+        raise VsError(f"dispatch counters: the library has {total}, the binding names {len(names)}")
+    return {name: int(buf[i]) for i, name in enumerate(names)}
+
+
+def total_path_count() -> int:
+    """VS_PATH_COUNT of the loaded library (vs_dispatch_counts' return value)."""
+    return int(lib().vs_dispatch_counts((c_i64 * 1)(), 0))
 
 
 def dispatch_reset() -> None:

@@ -69,6 +69,60 @@ class MSEMeanLoss(nn.Module):
         return mse_mean(pred, target)
 
 
+class _InfoNCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ref, pos, neg, log_inv_tau):
+        r, p, q = (t.detach().to(torch.float32).contiguous() for t in (ref, pos, neg))
+        dev = r.device
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        need = ctx.needs_input_grad
+        dr = torch.empty_like(r) if need[0] else None
+        dp = torch.empty_like(p) if need[1] else None
+        dq = torch.empty_like(q) if need[2] else None
+        lt = log_inv_tau.detach().to(torch.float32).reshape(1).contiguous() if log_inv_tau is not None else None
+        dt = torch.empty(1, dtype=torch.float32, device=dev) if lt is not None and need[3] else None
+        ops.info_nce(r, p, q, out, log_inv_tau=lt, d_ref=dr, d_pos=dp, d_neg=dq, grad_scale=1.0, d_log_inv_tau=dt)
+        ctx.grads = (dr, dp, dq, dt)
+        ctx.tau_shape = log_inv_tau.shape if log_inv_tau is not None else None
+        loss, pos_loss, neg_loss = out.unbind(0)
+        ctx.mark_non_differentiable(pos_loss, neg_loss)      # reported parts (they carry the detached shift c)
+        return loss, pos_loss, neg_loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _gp, _gn):
+        dr, dp, dq, dt = ctx.grads
+        ctx.grads = None
+        g = g.to(torch.float32)                               # scaled on the device (no host sync)
+        return (dr * g if dr is not None else None, dp * g if dp is not None else None,
+                dq * g if dq is not None else None, (dt * g).reshape(ctx.tau_shape) if dt is not None else None)
+
+
+class InfoNCE(nn.Module):
+    """The reference's contrastive criterion (`loss_fn_` -> `info_nce`, src/utils/loss_utils.py:3-21, 409-431)
+    on vs_info_nce: `criterion(ref, pos, neg) -> {'loss', 'pos_loss', 'neg_loss'}`, with ref / pos / neg the
+    ContrastViT plugin's output dicts ({'z', 'temp'}) or bare [n, E] embeddings.  fix_temp (default, as
+    src/pretrain.py uses it): tau = 1; otherwise tau = ref['temp'] and its gradient reaches `temperature`.
+    pos_loss and neg_loss are reported values (not differentiable); each rank uses its own negatives."""
+
+    def __init__(self, fix_temp: bool = True):
+        super().__init__()
+        self.fix_temp = bool(fix_temp)
+
+    def forward(self, ref, pos, neg):
+        temp = None
+        if isinstance(ref, dict):
+            temp = None if self.fix_temp else ref.get("temp")
+            ref, pos, neg = ref["z"], pos["z"], neg["z"]
+        L.require_device(ref, pos, neg)
+        if ref.dim() != 2 or pos.shape != ref.shape or neg.dim() != 2 or neg.shape[1] != ref.shape[1]:
+            raise ValueError("InfoNCE: ref / pos [n, E] and neg [m, E]")
+        # 1/tau = exp(log_inv_tau); temp = 1/exp(temperature), so this is the plugin's `temperature`
+        log_inv_tau = -torch.log(temp) if temp is not None else None
+        loss, pos_loss, neg_loss = _InfoNCEFn.apply(ref, pos, neg, log_inv_tau)
+        return {"loss": loss, "pos_loss": pos_loss, "neg_loss": neg_loss}
+
+
 LOSSES = {"poisson": poisson_nll_mean, "mse": mse_mean}
 
 

@@ -336,6 +336,97 @@ def token_pool_bwd(dpool, S, dx, dx_lp=None):
     return dx
 
 
+def cls_embed_fwd(patches, cls, table, x):
+    """x [G, P+1, D] f32: row 0 = cls + table[0], rows 1..P = the patch rows patches [G*P, D] (vs_cls_embed_fwd)."""
+    require_device(patches, cls, table, x)
+    G, T, D = x.shape
+    if patches.shape != (G * (T - 1), D) or table.shape != (T, D) or cls.numel() != D:
+        raise L.VsError("cls_embed_fwd: patches [G*P, D], cls [D], table [P+1, D], x [G, P+1, D]")
+    check(lib().vs_cls_embed_fwd(G, T - 1, D, patches.data_ptr(), cls.data_ptr(), table.data_ptr(), x.data_ptr(),
+                                 stream()), "vs_cls_embed_fwd")
+    return x
+
+
+def cls_embed_bwd(dx, d_cls, d_patches):
+    """d_cls [D] = sum over images (ascending) of dx[:, 0]; d_patches [G*P, D] (f32 or bf16) = dx[:, 1:]
+    (vs_cls_embed_bwd).  dx [G, P+1, D] f32, dense."""
+    require_device(dx, d_cls, d_patches)
+    G, T, D = dx.shape
+    if d_patches.shape != (G * (T - 1), D) or d_cls.numel() != D or not dx.is_contiguous():
+        raise L.VsError("cls_embed_bwd: dx [G, P+1, D] dense, d_cls [D], d_patches [G*P, D]")
+    check(lib().vs_cls_embed_bwd(L.dtype_code(d_patches.dtype), G, T - 1, D, dx.data_ptr(), d_cls.data_ptr(),
+                                 d_patches.data_ptr(), stream()), "vs_cls_embed_bwd")
+    return d_patches
+
+
+def embed_head_fwd(x, ldx, gamma, beta, eps, w, b, h, mean, rstd, z_raw, nrm, z):
+    """Final LayerNorm -> projection -> L2-normalise on one row per image (vs_embed_head_fwd): image g's
+    row starts at x.data_ptr() + g * ldx floats; h [G, D], mean / rstd / nrm [G], z_raw / z [G, E]."""
+    require_device(x, gamma, beta, w, b, h, mean, rstd, z_raw, nrm, z)
+    G, D = h.shape
+    E = w.shape[0]
+    if w.shape != (E, D) or z.shape != (G, E) or z_raw.shape != (G, E) or x.numel() < (G - 1) * ldx + D:
+        raise L.VsError("embed_head_fwd: w [E, D], h [G, D], z / z_raw [G, E], x at least (G-1)*ldx + D elements")
+    check(lib().vs_embed_head_fwd(G, D, E, x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(), float(eps),
+                                  w.data_ptr(), b.data_ptr(), h.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                  z_raw.data_ptr(), nrm.data_ptr(), z.data_ptr(), stream()), "vs_embed_head_fwd")
+    return z
+
+
+def embed_head_bwd_workspace_bytes(G, D, E):
+    return int(lib().vs_embed_head_bwd_workspace_bytes(G, D, E))
+
+
+def embed_head_bwd(dz, x, ldx, h, mean, rstd, z_raw, nrm, gamma, w, dx, dx_lp=None, dw=None, db=None, dgamma=None,
+                   dbeta=None, workspace=None):
+    """Backward of embed_head_fwd (vs_embed_head_bwd): dx [G, P+1, D] f32 gets the LayerNorm backward in row
+    0 of every image and zeros elsewhere, dx_lp (bf16, optional) its rounding; dw [E, D], db [E], dgamma,
+    dbeta [D] (all or none) are written, summed over images in ascending order."""
+    require_device(dz, x, h, mean, rstd, z_raw, nrm, gamma, w, dx, dx_lp, dw, db, dgamma, dbeta, workspace)
+    G, T, D = dx.shape
+    E = w.shape[0]
+    if (h.shape != (G, D) or dz.shape != (G, E) or z_raw.shape != (G, E) or not dx.is_contiguous()
+            or x.numel() < (G - 1) * ldx + D or (dx_lp is not None and dx_lp.numel() != dx.numel())
+            or (dw is not None and dw.shape != (E, D))):
+        raise L.VsError("embed_head_bwd: dz / z_raw [G, E], h [G, D], dx (and dx_lp) [G, P+1, D] dense, dw [E, D]")
+    if dw is not None and workspace is None:
+        workspace = torch.empty(embed_head_bwd_workspace_bytes(G, D, E) // 4 + 4, dtype=torch.float32, device=dx.device)
+    if workspace is not None and workspace.numel() * workspace.element_size() < embed_head_bwd_workspace_bytes(G, D, E):
+        raise L.VsError("embed_head_bwd: workspace too small")
+    check(lib().vs_embed_head_bwd(G, T - 1, D, E, dz.data_ptr(), x.data_ptr(), ldx, h.data_ptr(), mean.data_ptr(),
+                                  rstd.data_ptr(), z_raw.data_ptr(), nrm.data_ptr(), gamma.data_ptr(), w.data_ptr(),
+                                  dx.data_ptr(), ptr(dx_lp), ptr(dw), ptr(db), ptr(dgamma), ptr(dbeta), ptr(workspace),
+                                  stream()), "vs_embed_head_bwd")
+    return dx
+
+
+def info_nce_workspace_bytes(n, m):
+    return int(lib().vs_info_nce_workspace_bytes(n, m))
+
+
+def info_nce(ref, pos, neg, out, log_inv_tau=None, d_ref=None, d_pos=None, d_neg=None, grad_scale=1.0,
+             d_log_inv_tau=None, workspace=None):
+    """InfoNCE of loss_utils.py:409-431 (vs_info_nce): out f32[3] = (loss, pos_loss, neg_loss); ref / pos
+    [n, E], neg [m, E] f32 dense; log_inv_tau a device scalar (None: tau = 1); gradients optional."""
+    require_device(ref, pos, neg, out, log_inv_tau, d_ref, d_pos, d_neg, d_log_inv_tau, workspace)
+    n, E = ref.shape
+    m = neg.shape[0]
+    for t, shape in ((ref, (n, E)), (pos, (n, E)), (neg, (m, E)), (d_ref, (n, E)), (d_pos, (n, E)), (d_neg, (m, E))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise L.VsError("info_nce: ref / pos [n, E], neg [m, E] (and their gradients) dense float32")
+    if out.numel() < 3 or out.dtype != torch.float32:
+        raise L.VsError("info_nce: out must hold three float32")
+    need = info_nce_workspace_bytes(n, m)
+    if workspace is None:
+        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=ref.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise L.VsError("info_nce: workspace too small")
+    check(lib().vs_info_nce(n, m, E, ref.data_ptr(), pos.data_ptr(), neg.data_ptr(), ptr(log_inv_tau), out.data_ptr(),
+                            ptr(d_ref), ptr(d_pos), ptr(d_neg), float(grad_scale), ptr(d_log_inv_tau),
+                            workspace.data_ptr(), stream()), "vs_info_nce")
+    return out
+
+
 def poisson_nll(log_rate, target, loss_out, dx=None, grad_scale=1.0, workspace=None):
     require_device(log_rate, target, loss_out)
     n = log_rate.numel()

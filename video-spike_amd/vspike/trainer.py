@@ -43,6 +43,60 @@ def build_optimizer(model, config, total_steps: int, world: int = 1):
     return opt, sched
 
 
+class ContrastTrainer:
+    """The contrastive pretraining step of `src/trainer/contrast.py:80-122` for the ContrastViT plugin:
+
+        ref, pos, neg = model(ref), model(pos), model(neg); loss = criterion(ref, pos, neg)['loss']
+        loss.backward(); optimizer.step()                      # no scheduler in the reference
+
+    `step` runs it fused: the three (n, C, H, W) batches go through ONE 3n forward, one vs_info_nce and
+    one backward.  No op couples images before the loss, so the result is the three-call form's
+    (`step_three_calls`, kept for comparison and for callers that drive the model themselves)."""
+
+    def __init__(self, model, optimizer, lr_scheduler=None, criterion=None, exchange: Optional[GradExchange] = None):
+        from .loss import InfoNCE
+        self.model, self.optimizer, self.lr_scheduler, self.exchange = model, optimizer, lr_scheduler, exchange
+        self.criterion = criterion if criterion is not None else InfoNCE(fix_temp=getattr(model, "fix_temp", True))
+
+    def _finish(self, res):
+        if self.exchange is not None:
+            self.exchange.finish()
+        self.optimizer.step()
+        if self.lr_scheduler is not None:
+            self.lr_scheduler.step()
+        self.optimizer.zero_grad(set_to_none=True)
+        return {k: v.detach() for k, v in res.items()}
+
+    def step(self, ref, pos, neg) -> dict:
+        n = ref.shape[0]
+        if pos.shape != ref.shape or neg.shape[1:] != ref.shape[1:]:
+            raise ValueError("ContrastTrainer.step: ref / pos (n, C, H, W) and neg (m, C, H, W)")
+        out = self.model(torch.cat([ref, pos, neg], dim=0))
+        z, temp = out["z"], out["temp"]
+        res = self.criterion({"z": z[:n], "temp": temp}, {"z": z[n:2 * n], "temp": temp}, {"z": z[2 * n:], "temp": temp})
+        res["loss"].backward()
+        return self._finish(res)
+
+    def step_three_calls(self, ref, pos, neg) -> dict:
+        """The reference trainer's literal form: three forwards alive before one backward.  Refused while a
+        data-parallel gradient sink is attached (the sink reduces one backward per step)."""
+        res = self.criterion(self.model(ref), self.model(pos), self.model(neg))
+        res["loss"].backward()
+        return self._finish(res)
+
+    @torch.no_grad()
+    def transform(self, batches: Iterable) -> torch.Tensor:
+        """`src/trainer/contrast.py:165-206`: the stacked embeddings z of every batch (tensors, or dicts
+        with the images under 'ref'), in order.  The model's train / eval mode is restored afterwards."""
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            zs = [self.model(b["ref"] if isinstance(b, dict) else b)["z"] for b in batches]
+        finally:
+            self.model.train(was_training)
+        return torch.cat(zs, dim=0)
+
+
 class Trainer:
     def __init__(self, model, optimizer, lr_scheduler=None, config=None, criterion=None,
                  exchange: Optional[GradExchange] = None):

@@ -559,11 +559,29 @@ class VideoMAE(nn.Module):
     def _encoder_backward(self, st, g, bkey, g_enc):
         """The encoder blocks in reverse and the patch embedding, from the gradient of the encoder
         output in g["dxA"] (and its bf16 copy g["dxA_lp"]); weight gradients go into g_enc."""
+        cfg = self.backbone
+        lay, le = self.layout, self.layout.enc
+        act = st["act"]
+        lp = self.compute_dtype != torch.float32
+        Ge = lambda n: le.view(g_enc, n)  # noqa: E731
+        dx, dx_lp = self._blocks_backward(st, g, bkey, g_enc)
+        # patch embedding: dW = dx0^T cols, db = colsum(dx0); the position table is fixed
+        if "cols" not in act:   # cols = the tubelet gather of the pixels, done in the dW's operand load
+            ops.patch_embed_dw(st["pixels"], dx_lp, Ge("patch_w"), Ge("patch_b"), cfg.tubelet_size, cfg.patch_size,
+                               workspace=g["patch_ws"])
+        elif lp:   # bias gradient fused as row sums of dx^T (fixed-order, like every block's dW)
+            ops.linear_dw(dx_lp, act["cols"], Ge("patch_w"), db=Ge("patch_b"), workspace=g.get("patch_ws"))
+        else:
+            ops.linear_dw(dx, act["cols"], Ge("patch_w"), db=Ge("patch_b"))
+        self._ready(self.enc_flat, 0, lay.layer_ranges[0][0] if lay.layer_ranges else self.enc_flat.numel())
+
+    def _blocks_backward(self, st, g, bkey, g_enc):
+        """The encoder blocks in reverse from g["dxA"] / g["dxA_lp"]; returns the gradient of the first
+        block's input and its bf16 copy (None in fp32)."""
         cfg, dt = self.backbone, self.compute_dtype
         B = st["B"]
         N, Lyr = cfg.num_tokens, cfg.num_hidden_layers
         lay, le = self.layout, self.layout.enc
-        act = st["act"]
         dev = g_enc.device
         lp = dt != torch.float32
         gs_cache = self._caches()[2]
@@ -616,15 +634,7 @@ class VideoMAE(nn.Module):
             prev = i
         if prev is not None:
             self._ready(self.enc_flat, *lay.layer_ranges[prev])
-        # patch embedding: dW = dx0^T cols, db = colsum(dx0); the position table is fixed
-        if "cols" not in act:   # cols = the tubelet gather of the pixels, done in the dW's operand load
-            ops.patch_embed_dw(st["pixels"], dx_lp, Ge("patch_w"), Ge("patch_b"), cfg.tubelet_size, cfg.patch_size,
-                               workspace=g["patch_ws"])
-        elif lp:   # bias gradient fused as row sums of dx^T (fixed-order, like every block's dW)
-            ops.linear_dw(dx_lp, act["cols"], Ge("patch_w"), db=Ge("patch_b"), workspace=g.get("patch_ws"))
-        else:
-            ops.linear_dw(dx, act["cols"], Ge("patch_w"), db=Ge("patch_b"))
-        self._ready(self.enc_flat, 0, lay.layer_ranges[0][0] if lay.layer_ranges else self.enc_flat.numel())
+        return dx, dx_lp
 
 
 class _VideoMAEFn(torch.autograd.Function):
