@@ -32,6 +32,7 @@ extern "C" {
 #define VS_F32 0
 #define VS_BF16 1
 #define VS_U8 2   /* raw video frames only (vs_video_preprocess) */
+#define VS_F64 4  /* the RRR validation only (vs_rrr_*): y / gt as f64 */
 #define VS_FP8 3  /* OCP e4m3 with MX (E8M0 per 32 k) scales: vs_gemm_mxfp8 operands; as vs_vit_layer.dtype:
                      bf16 everywhere + MX-FP8 forward block products (BASELINE C5) */
 
@@ -556,6 +557,36 @@ int vs_info_nce(int64_t n, int64_t m, int64_t E, const float* ref, const float* 
                 float* d_log_inv_tau, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Reduced-rank regression validation of the contrastive path (csrc/rrr.hip):
+ * src/model/rrr.py:79-175 (RRRGD's loss and the L-BFGS closure) and the scoring half of train_rrr
+ * (src/utils/utils.py:411-447).  K trials, T bins, N neurons, C features, r components:
+ *   X [K, T, C+1] f64 with a last column of ones;  y / gt [K, T, N], VS_F32 or VS_F64 (`*_dtype`);
+ *   U [N, C, r], V [r, T], b [N, 1, T] f64.   beta[n,c,t] = sum_j U[n,c,j] V[j,t] (c < C), beta[n,C,t] = b[n,t];
+ *   yhat[k,t,n] = sum_c X[k,t,c] beta[n,c,t];  loss = sum (yhat - y)^2 + l2 sum beta^2 (b^2 included, rrr.py:154-155).
+ * These are the ABI's first `const double*` arguments: every operand but y / gt is f64, and all arithmetic
+ * and accumulation is f64.  1 <= C <= 32 and 1 <= r <= 8, else VS_EINVAL.  No atomics; reductions run in an
+ * order fixed by the extents, so equal inputs give bitwise equal outputs.  Pointers 8-byte aligned, the
+ * workspace 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+/* loss (device f64[1]) and, when dU / dV / db are given (all three, or all NULL = loss only: the reference's
+   mses_val with l2 = 0), dU [N, C, r], dV [r, T], db [N, 1, T], WRITTEN.  y and X are read once; nothing of
+   size K T N is written.  workspace: >= vs_rrr_loss_grad_workspace_bytes(K, T, N, C). */
+size_t vs_rrr_loss_grad_workspace_bytes(int64_t K, int64_t T, int64_t N, int64_t C);
+int vs_rrr_loss_grad(int64_t K, int64_t T, int64_t N, int64_t C, int64_t r, const double* X, const void* y,
+                     int32_t y_dtype, const double* U, const double* V, const double* b, double l2, double* loss,
+                     double* dU, double* dV, double* db, void* workspace, void* stream);
+/* pred = max(yhat * std_y + mean_y, 1e-3) on the held-out X (mean_y, std_y [T, N] f64; pred [K, T, N] f64, may
+   be NULL) against the raw counts gt.  Per neuron: bps = bits_per_spike over all (k, t) (metric_utils.py:78-102:
+   null rate = the neuron's mean count, 0 -> 1e-9, divided by its spike sum and ln 2, +-inf -> NaN) and r2 = the
+   NaN-ignoring mean over trials of sklearn r2_score(gt[k,:,n], pred[k,:,n]) (force_finite: SS_res = 0 -> 1,
+   else SS_tot = 0 -> 0; T < 2 -> NaN).  out (device f64[2]) = NaN-ignoring means over neurons of bps (co_bps)
+   and r2.  workspace: >= vs_rrr_score_workspace_bytes(K, N). */
+size_t vs_rrr_score_workspace_bytes(int64_t K, int64_t N);
+int vs_rrr_score(int64_t K, int64_t T, int64_t N, int64_t C, int64_t r, const double* X, const double* U,
+                 const double* V, const double* b, const double* mean_y, const double* std_y, const void* gt,
+                 int32_t gt_dtype, double* pred, double* bps, double* r2, double* out, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Trial shards (host side of the input path; replaces the per-trial webdataset tars of
  * src/prepare_data.py:210-235 read by src/loader/base.py:21-41).  Fixed-size records: raw uint8
  * frames (T, C, H, W) + f32 spike counts (ap_rows, ap_cols) + a 64-byte "<eid>_<trial>" key.
@@ -588,7 +619,7 @@ const char* vs_shard_last_error(void);
 #define VS_TIMER_LN_FWD   4   /* vs_layernorm_fwd */
 #define VS_TIMER_LN_BWD   5   /* vs_layernorm_bwd (+ its partial-sum reduction) */
 #define VS_TIMER_ADAMW    6   /* vs_adamw */
-#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd), vs_token_pool_*, vs_cls_embed_*, vs_embed_head_*, vs_info_nce */
+#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd), vs_token_pool_*, vs_cls_embed_*, vs_embed_head_*, vs_info_nce, vs_rrr_* */
 /* per-product tags of the ViT block executor (vs_vit_layer_fwd / _bwd): its vs_gemm calls are
    charged to these instead of VS_TIMER_GEMM / VS_TIMER_GEMM_DW, so every product has its own timer */
 #define VS_TIMER_FWD_QKV   8   /* qkv = h1 Wqkv^T + b          (mv:233-236) */

@@ -1,0 +1,513 @@
+// rrr.hip — the reduced-rank regression (RRR) validation of the contrastive pretraining path:
+//   src/model/rrr.py:79-155,164-175   RRRGD's beta / predict / MSE / l2 term and the L-BFGS closure
+//   src/utils/utils.py:411-447        train_rrr's scoring (clip, bits_per_spike, sklearn r2_score per trial)
+// K trials, T bins, N neurons, C features (X carries a trailing column of ones), r components:
+//   beta[n,c,t] = sum_j U[n,c,j] V[j,t] (c < C),  beta[n,C,t] = b[n,t]
+//   yhat[k,t,n] = sum_c X[k,t,c] beta[n,c,t],     loss = sum (yhat - y)^2 + l2 sum beta^2   (b^2 included)
+// Everything is f64 (y / gt may be f32: converted in the load).  No atomics; every reduction runs in an order
+// fixed by the extents alone, so two calls on the same inputs agree bitwise.
+//
+// vs_rrr_loss_grad, 4 launches (2 in loss-only mode):
+//   1. rrr_accum_kernel    block = 64 neurons x 4 waves, one bin t.  A thread owns neuron n and keeps beta[n,:,t]
+//                          in registers; X[k,t,:] is wave-uniform (scalar loads), y[k,t,n..n+63] one contiguous
+//                          row piece.  Each wave takes a slice of the trials and accumulates sq = sum res^2 and
+//                          G[c] = sum X[k,t,c] 2 res; waves 1..3 hand theirs to wave 0 through LDS (added in wave
+//                          order).  When T * ceil(N/64) is a small grid the trials are also split over S blocks
+//                          (ordered partials).  Writes part[s][t][c][n] (rows 0..C = G, row C+1 = sq):
+//                          S T (C+2) N doubles, nothing of size K T N.  y and X are read exactly once.
+//   2. rrr_reduce_t_kernel block = 64 neurons x 4 waves, one row c.  Sums the S partials, forms
+//                          H = G + 2 l2 beta (kept [t][c][n] for step 3), db = H[:,C,:], and over its slice of the
+//                          bins dU[n,c,:] += H V[:,t] and the loss terms; waves combine through LDS in wave order.
+//   3. rrr_dv_kernel       block = one bin t: dV[:,t] = sum_{n,c} U[n,c,:] H[t][c][n] (strided + LDS tree).
+//   4. rrr_loss_kernel     one block: loss = sum of the (C+2) N loss terms (strided + LDS tree).
+// vs_rrr_score: rrr_score_kernel (block = 64 neurons x 4 waves, wave = a slice of the held-out trials; a thread
+//   walks its neuron's T bins of one trial, so the trial's R^2 is complete in registers) + rrr_score_final_kernel.
+#include <math.h>
+
+#include "common.h"
+
+namespace vs {
+
+constexpr int kRrrMaxC = 32;
+constexpr int kRrrMaxR = 8;
+constexpr int kRrrWaves = 4;
+constexpr int kRrrMaxSplit = 16;
+
+template <typename YT> __device__ __forceinline__ double ld_f64(const YT* p) { return (double)*p; }
+__device__ __forceinline__ int64_t dcdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// beta[n,c,t] for c < C (u = U[n,c,:] in registers)
+__device__ __forceinline__ double rrr_beta(const double* u, const double* __restrict__ V, int r, int64_t T, int64_t t) {
+  double s = 0.0;
+#pragma unroll
+  for (int j = 0; j < kRrrMaxR; ++j)
+    if (j < r) s = fma(u[j], V[(int64_t)j * T + t], s);
+  return s;
+}
+
+// CP: C + 1 rounded up to a compiled size (rows C+1 .. CP-1 are zeros)
+template <typename YT, int CP, bool GRAD>
+__global__ __launch_bounds__(256) void rrr_accum_kernel(int64_t K, int64_t T, int64_t N, int C, int r, int64_t kper,
+                                                        const double* __restrict__ X, const YT* __restrict__ y,
+                                                        const double* __restrict__ U, const double* __restrict__ V,
+                                                        const double* __restrict__ b, double* __restrict__ part) {
+  constexpr int kVals = GRAD ? CP + 1 : 1;
+  __shared__ double red[(kRrrWaves - 1) * kVals * 64];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t t = blockIdx.y;
+  const int64_t n = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = n < N;
+  const int C1 = C + 1;
+  double beta[CP];
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    beta[c] = 0.0;
+    if (live && c < C) {
+      double u[kRrrMaxR];
+#pragma unroll
+      for (int j = 0; j < kRrrMaxR; ++j) u[j] = j < r ? U[(n * C + c) * r + j] : 0.0;
+      beta[c] = rrr_beta(u, V, r, T, t);
+    } else if (live && c == C) {
+      beta[c] = b[n * T + t];
+    }
+  }
+  double G[GRAD ? CP : 1];
+#pragma unroll
+  for (int c = 0; c < (GRAD ? CP : 1); ++c) G[c] = 0.0;
+  double sq = 0.0;
+  const int64_t k0 = ((int64_t)blockIdx.z * kRrrWaves + w) * kper;
+  const int64_t k1 = k0 + kper < K ? k0 + kper : K;
+#pragma unroll 4
+  for (int64_t k = k0; k < k1; ++k) {
+    const double* xr = X + (k * T + t) * C1;
+    const double yv = live ? ld_f64(y + (k * T + t) * N + n) : 0.0;
+    double x[CP];
+#pragma unroll
+    for (int c = 0; c < CP; ++c) x[c] = c < C1 ? xr[c] : 0.0;
+    double yh = 0.0;
+#pragma unroll
+    for (int c = 0; c < CP; ++c) yh = fma(x[c], beta[c], yh);
+    const double res = yh - yv;
+    sq = fma(res, res, sq);
+    if (GRAD) {
+      const double g = 2.0 * res;
+#pragma unroll
+      for (int c = 0; c < CP; ++c) G[c] = fma(x[c], g, G[c]);
+    }
+  }
+  if (w > 0) {
+    double* p = red + (size_t)(w - 1) * kVals * 64 + lane;
+    p[0] = sq;
+    if (GRAD) {
+#pragma unroll
+      for (int c = 0; c < CP; ++c) p[(c + 1) * 64] = G[c];
+    }
+  }
+  __syncthreads();
+  if (w == 0 && live) {
+    for (int v = 1; v < kRrrWaves; ++v) {
+      const double* p = red + (size_t)(v - 1) * kVals * 64 + lane;
+      sq += p[0];
+      if (GRAD) {
+#pragma unroll
+        for (int c = 0; c < CP; ++c) G[c] += p[(c + 1) * 64];
+      }
+    }
+    double* o = part + (((int64_t)blockIdx.z * T + t) * (C + 2)) * N + n;
+    if (GRAD) {
+#pragma unroll
+      for (int c = 0; c < CP; ++c)
+        if (c < C1) o[(int64_t)c * N] = G[c];
+    }
+    o[(int64_t)(C + 1) * N] = sq;
+  }
+}
+
+// grid (ceil(N/64), C+2): row c <= C of H / dU / db and its l2 term, row C+1 the squared residuals.
+// grad == 0 (loss only): rows 0..C have no partials and only their l2 terms are formed.
+__global__ __launch_bounds__(256) void rrr_reduce_t_kernel(int64_t T, int64_t N, int C, int r, int S, double l2, int grad,
+                                                           const double* __restrict__ part,
+                                                           const double* __restrict__ U, const double* __restrict__ V,
+                                                           const double* __restrict__ b, double* __restrict__ H,
+                                                           double* __restrict__ dU, double* __restrict__ db,
+                                                           double* __restrict__ lossp) {
+  __shared__ double red[(kRrrWaves - 1) * (kRrrMaxR + 1) * 64];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int c = blockIdx.y;
+  const int64_t n = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = n < N;
+  const int C1 = C + 1;
+  const int64_t tper = dcdiv(T, kRrrWaves);
+  const int64_t t0 = (int64_t)w * tper;
+  const int64_t t1 = t0 + tper < T ? t0 + tper : T;
+  double u[kRrrMaxR], du[kRrrMaxR];
+#pragma unroll
+  for (int j = 0; j < kRrrMaxR; ++j) {
+    u[j] = (live && c < C && j < r) ? U[(n * C + c) * r + j] : 0.0;
+    du[j] = 0.0;
+  }
+  double term = 0.0;  // sum beta^2 (rows 0..C) or sum res^2 (row C+1)
+  if (live) {
+    for (int64_t t = t0; t < t1; ++t) {
+      double g = 0.0;
+      if (grad || c == C1)
+        for (int s = 0; s < S; ++s) g += part[(((int64_t)s * T + t) * (C + 2) + c) * N + n];
+      if (c == C1) {
+        term += g;
+        continue;
+      }
+      const double be = c < C ? rrr_beta(u, V, r, T, t) : b[n * T + t];
+      term = fma(be, be, term);
+      if (grad) {
+        const double h = fma(2.0 * l2, be, g);
+        H[(t * C1 + c) * N + n] = h;
+        if (c == C) {
+          db[n * T + t] = h;
+        } else {
+#pragma unroll
+          for (int j = 0; j < kRrrMaxR; ++j)
+            if (j < r) du[j] = fma(h, V[(int64_t)j * T + t], du[j]);
+        }
+      }
+    }
+  }
+  if (w > 0) {
+    double* p = red + (size_t)(w - 1) * (kRrrMaxR + 1) * 64 + lane;
+    p[0] = term;
+#pragma unroll
+    for (int j = 0; j < kRrrMaxR; ++j) p[(j + 1) * 64] = du[j];
+  }
+  __syncthreads();
+  if (w == 0 && live) {
+    for (int v = 1; v < kRrrWaves; ++v) {
+      const double* p = red + (size_t)(v - 1) * (kRrrMaxR + 1) * 64 + lane;
+      term += p[0];
+#pragma unroll
+      for (int j = 0; j < kRrrMaxR; ++j) du[j] += p[(j + 1) * 64];
+    }
+    lossp[(int64_t)c * N + n] = c == C1 ? term : l2 * term;
+    if (grad && c < C) {
+#pragma unroll
+      for (int j = 0; j < kRrrMaxR; ++j)
+        if (j < r) dU[(n * C + c) * r + j] = du[j];
+    }
+  }
+}
+
+// fixed-shape block reduction (256 threads); every thread gets the sum
+__device__ double rrr_block_sum(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  const double out = red[0];
+  __syncthreads();
+  return out;
+}
+
+// block t: dV[j,t] = sum over i = c N + n (c < C) of U[n,c,j] H[t][c][n]
+__global__ __launch_bounds__(256) void rrr_dv_kernel(int64_t T, int64_t N, int C, int r, const double* __restrict__ U,
+                                                     const double* __restrict__ H, double* __restrict__ dV) {
+  __shared__ double red[256];
+  const int64_t t = blockIdx.x;
+  const double* h = H + t * (C + 1) * N;
+  double acc[kRrrMaxR];
+#pragma unroll
+  for (int j = 0; j < kRrrMaxR; ++j) acc[j] = 0.0;
+  for (int64_t i = threadIdx.x; i < (int64_t)C * N; i += 256) {
+    const int64_t c = i / N, n = i - c * N;
+    const double hv = h[i];
+    const double* up = U + (n * C + c) * r;
+#pragma unroll
+    for (int j = 0; j < kRrrMaxR; ++j)
+      if (j < r) acc[j] = fma(up[j], hv, acc[j]);
+  }
+  for (int j = 0; j < r; ++j) {
+    const double s = rrr_block_sum(acc[j], red);
+    if (threadIdx.x == 0) dV[(int64_t)j * T + t] = s;
+  }
+}
+
+__global__ __launch_bounds__(256) void rrr_loss_kernel(int64_t count, const double* __restrict__ lossp,
+                                                       double* __restrict__ loss) {
+  __shared__ double red[256];
+  double a = 0.0;
+  for (int64_t i = threadIdx.x; i < count; i += 256) a += lossp[i];
+  a = rrr_block_sum(a, red);
+  if (threadIdx.x == 0) loss[0] = a;
+}
+
+struct RrrWs {
+  int S;
+  int64_t kper;
+  size_t part, H, lossp, total;  // byte offsets
+};
+static RrrWs rrr_ws(int64_t K, int64_t T, int64_t N, int64_t C) {
+  RrrWs w;
+  const int64_t blocks = T * cdiv(N, 64);
+  int64_t S = blocks >= 512 ? 1 : cdiv(512, blocks);
+  const int64_t cap = K / (2 * kRrrWaves);  // at least two trials per wave before splitting further
+  if (S > cap) S = cap;
+  if (S > kRrrMaxSplit) S = kRrrMaxSplit;
+  if (S < 1) S = 1;
+  w.kper = cdiv(K, S * kRrrWaves);
+  w.S = (int)cdiv(K, w.kper * kRrrWaves);
+  auto al = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+  size_t off = 0;
+  w.part = off;  off += al((size_t)w.S * T * (C + 2) * N * 8);
+  w.H = off;     off += al((size_t)T * (C + 1) * N * 8);
+  w.lossp = off; off += al((size_t)(C + 2) * N * 8);
+  w.total = off;
+  return w;
+}
+
+template <typename YT, int CP>
+static void rrr_launch_accum(bool grad, dim3 grid, hipStream_t s, int64_t K, int64_t T, int64_t N, int C, int r,
+                             int64_t kper, const double* X, const void* y, const double* U, const double* V,
+                             const double* b, double* part) {
+  if (grad)
+    hipLaunchKernelGGL((rrr_accum_kernel<YT, CP, true>), grid, dim3(256), 0, s, K, T, N, C, r, kper, X, (const YT*)y, U,
+                       V, b, part);
+  else
+    hipLaunchKernelGGL((rrr_accum_kernel<YT, CP, false>), grid, dim3(256), 0, s, K, T, N, C, r, kper, X, (const YT*)y,
+                       U, V, b, part);
+}
+template <typename YT>
+static void rrr_dispatch_accum(int C1, bool grad, dim3 grid, hipStream_t s, int64_t K, int64_t T, int64_t N, int C,
+                               int r, int64_t kper, const double* X, const void* y, const double* U, const double* V,
+                               const double* b, double* part) {
+#define VS_RRR_CASE(CP)                                                                       \
+  if (C1 <= CP) {                                                                             \
+    rrr_launch_accum<YT, CP>(grad, grid, s, K, T, N, C, r, kper, X, y, U, V, b, part);        \
+    return;                                                                                   \
+  }
+  VS_RRR_CASE(2) VS_RRR_CASE(4) VS_RRR_CASE(6) VS_RRR_CASE(8) VS_RRR_CASE(12) VS_RRR_CASE(16) VS_RRR_CASE(24)
+  VS_RRR_CASE(33)
+#undef VS_RRR_CASE
+}
+
+// ---- scoring -------------------------------------------------------------------------------
+// stats per neuron: [0] spike sum, [1] sum pred, [2] sum gt log pred, [3] sum R^2 over non-NaN trials, [4] their count
+constexpr int kScoreStats = 5;
+constexpr int kScoreMaxChunks = 256;
+
+// grid (ceil(N/64), chunks of the trials); wave w of a block takes a slice of the chunk.  stat [chunk][5][N].
+template <typename YT>
+__global__ __launch_bounds__(256) void rrr_score_kernel(int64_t K, int64_t T, int64_t N, int C, int r, int64_t kchunk,
+                                                        const double* __restrict__ X, const double* __restrict__ U,
+                                                        const double* __restrict__ V, const double* __restrict__ b,
+                                                        const double* __restrict__ mean_y,
+                                                        const double* __restrict__ std_y, const YT* __restrict__ gt,
+                                                        double* __restrict__ pred, double* __restrict__ stat) {
+  __shared__ double red[(kRrrWaves - 1) * kScoreStats * 64];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t n = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = n < N;
+  const int C1 = C + 1;
+  const int64_t kw = dcdiv(kchunk, kRrrWaves);
+  const int64_t kend = ((int64_t)blockIdx.y + 1) * kchunk < K ? ((int64_t)blockIdx.y + 1) * kchunk : K;
+  const int64_t k0 = (int64_t)blockIdx.y * kchunk + (int64_t)w * kw;
+  const int64_t k1 = k0 + kw < kend ? k0 + kw : kend;
+  double st[kScoreStats] = {0, 0, 0, 0, 0};
+  if (live) {
+    const double* un = U + n * C * r;
+    for (int64_t k = k0; k < k1; ++k) {
+      double sy = 0.0, res = 0.0;
+      for (int64_t t = 0; t < T; ++t) {
+        const double* xr = X + (k * T + t) * C1;
+        double yh = 0.0;
+        for (int c = 0; c < C; ++c) yh = fma(xr[c], rrr_beta(un + c * r, V, r, T, t), yh);
+        yh = fma(xr[C], b[n * T + t], yh);
+        double p = fma(yh, std_y[t * N + n], mean_y[t * N + n]);
+        p = p < 1e-3 ? 1e-3 : p;   // np.clip(pred, 1e-3, None): a NaN stays a NaN
+        const int64_t at = (k * T + t) * N + n;
+        if (pred) pred[at] = p;
+        const double g = ld_f64(gt + at);
+        st[0] += g;
+        st[1] += p;
+        st[2] = fma(g, log(p), st[2]);
+        sy += g;
+        const double d = g - p;
+        res = fma(d, d, res);
+      }
+      // SS_tot about the trial's own mean, in a second pass over the T counts (no cancellation)
+      const double m = sy / (double)T;
+      double tot = 0.0;
+      for (int64_t t = 0; t < T; ++t) {
+        const double e = ld_f64(gt + (k * T + t) * N + n) - m;
+        tot = fma(e, e, tot);
+      }
+      double v;   // sklearn r2_score, 1-D, force_finite
+      if (T < 2 || res != res || tot != tot) v = __builtin_nan("");
+      else if (res == 0.0) v = 1.0;
+      else if (tot == 0.0) v = 0.0;
+      else v = 1.0 - res / tot;
+      if (v == v) {
+        st[3] += v;
+        st[4] += 1.0;
+      }
+    }
+  }
+  if (w > 0) {
+#pragma unroll
+    for (int i = 0; i < kScoreStats; ++i) red[((size_t)(w - 1) * kScoreStats + i) * 64 + lane] = st[i];
+  }
+  __syncthreads();
+  if (w == 0 && live) {
+    for (int v = 1; v < kRrrWaves; ++v)
+#pragma unroll
+      for (int i = 0; i < kScoreStats; ++i) st[i] += red[((size_t)(v - 1) * kScoreStats + i) * 64 + lane];
+#pragma unroll
+    for (int i = 0; i < kScoreStats; ++i) stat[((int64_t)blockIdx.y * kScoreStats + i) * N + n] = st[i];
+  }
+}
+
+// one block: per neuron bps and R^2 (chunks added in ascending order), then their NaN-ignoring means;
+// out[0] = co_bps, out[1] = mean R^2
+__global__ __launch_bounds__(256) void rrr_score_final_kernel(int64_t K, int64_t T, int64_t N, int chunks,
+                                                              const double* __restrict__ stat,
+                                                              double* __restrict__ bps, double* __restrict__ r2,
+                                                              double* __restrict__ out) {
+  __shared__ double red[256];
+  const double nan = __builtin_nan("");
+  const double cnt = (double)K * (double)T;
+  double sb = 0, nb = 0, sr = 0, nr = 0;
+  for (int64_t n = threadIdx.x; n < N; n += 256) {
+    double st[kScoreStats] = {0, 0, 0, 0, 0};
+    for (int ch = 0; ch < chunks; ++ch)
+#pragma unroll
+      for (int i = 0; i < kScoreStats; ++i) st[i] += stat[((int64_t)ch * kScoreStats + i) * N + n];
+    const double S = st[0];
+    double m = S / cnt;                       // the null model: the neuron's mean count
+    if (m == 0.0) m = 1e-9;
+    const double nll_null = cnt * m - S * log(m);
+    const double nll_model = st[1] - st[2];   // the log(n!) terms of both likelihoods cancel
+    double v = (nll_null - nll_model) / S / 0.69314718055994530942;
+    if (isinf(v)) v = nan;
+    const double q = st[4] > 0 ? st[3] / st[4] : nan;
+    bps[n] = v;
+    r2[n] = q;
+    if (v == v) {
+      sb += v;
+      nb += 1;
+    }
+    if (q == q) {
+      sr += q;
+      nr += 1;
+    }
+  }
+  sb = rrr_block_sum(sb, red);
+  nb = rrr_block_sum(nb, red);
+  sr = rrr_block_sum(sr, red);
+  nr = rrr_block_sum(nr, red);
+  if (threadIdx.x == 0) {
+    out[0] = nb > 0 ? sb / nb : nan;
+    out[1] = nr > 0 ? sr / nr : nan;
+  }
+}
+
+struct ScoreWs {
+  int chunks;
+  int64_t kchunk;
+  size_t total;
+};
+static ScoreWs score_ws(int64_t K, int64_t N) {
+  ScoreWs w;
+  int64_t ch = cdiv(K, kRrrWaves);
+  if (ch > kScoreMaxChunks) ch = kScoreMaxChunks;
+  w.kchunk = cdiv(K, ch);
+  w.chunks = (int)cdiv(K, w.kchunk);
+  w.total = ((size_t)w.chunks * kScoreStats * N * 8 + 255) / 256 * 256;
+  return w;
+}
+
+static bool rrr_dims_ok(int64_t K, int64_t T, int64_t N, int64_t C, int64_t r) {
+  return K > 0 && T > 0 && N > 0 && C >= 1 && C <= kRrrMaxC && r >= 1 && r <= kRrrMaxR && T <= 65535 &&
+         cdiv(N, 64) <= 0x7fffffff;
+}
+
+}  // namespace vs
+
+using namespace vs;
+
+extern "C" size_t vs_rrr_loss_grad_workspace_bytes(int64_t K, int64_t T, int64_t N, int64_t C) {
+  if (K <= 0 || T <= 0 || N <= 0 || C < 1 || C > kRrrMaxC) return 0;
+  return rrr_ws(K, T, N, C).total;
+}
+
+extern "C" int vs_rrr_loss_grad(int64_t K, int64_t T, int64_t N, int64_t C, int64_t r, const double* X, const void* y,
+                                int32_t y_dtype, const double* U, const double* V, const double* b, double l2,
+                                double* loss, double* dU, double* dV, double* db, void* workspace, void* stream) {
+  VS_REQUIRE(C >= 1 && C <= kRrrMaxC, "vs_rrr_loss_grad: 1 <= C <= 32 features (without the bias column)");
+  VS_REQUIRE(r >= 1 && r <= kRrrMaxR, "vs_rrr_loss_grad: 1 <= r <= 8 components");
+  VS_REQUIRE(rrr_dims_ok(K, T, N, C, r), "vs_rrr_loss_grad: K, T, N must be positive (T <= 65535)");
+  VS_REQUIRE(y_dtype == VS_F32 || y_dtype == VS_F64, "vs_rrr_loss_grad: y must be f32 or f64");
+  VS_REQUIRE(X && y && U && V && b && loss && workspace, "vs_rrr_loss_grad: null pointer");
+  const bool grad = dU || dV || db;
+  VS_REQUIRE(!grad || (dU && dV && db), "vs_rrr_loss_grad: dU, dV, db are given together or not at all");
+  VS_REQUIRE((((uintptr_t)workspace) & 15u) == 0, "vs_rrr_loss_grad: workspace must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const RrrWs w = rrr_ws(K, T, N, C);
+  char* ws = (char*)workspace;
+  double* part = (double*)(ws + w.part);
+  double* H = (double*)(ws + w.H);
+  double* lossp = (double*)(ws + w.lossp);
+  ScopedTimer timer(VS_TIMER_MISC, s,
+                    (double)K * T * ((double)N * (y_dtype == VS_F32 ? 4.0 : 8.0) + (C + 1) * 8.0));
+  const dim3 grid((unsigned)cdiv(N, 64), (unsigned)T, (unsigned)w.S);
+  if (y_dtype == VS_F32)
+    rrr_dispatch_accum<float>((int)C + 1, grad, grid, s, K, T, N, (int)C, (int)r, w.kper, X, y, U, V, b, part);
+  else
+    rrr_dispatch_accum<double>((int)C + 1, grad, grid, s, K, T, N, (int)C, (int)r, w.kper, X, y, U, V, b, part);
+  VS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rrr_reduce_t_kernel, dim3((unsigned)cdiv(N, 64), (unsigned)(C + 2)), dim3(256), 0, s, T, N, (int)C,
+                     (int)r, w.S, l2, grad ? 1 : 0, (const double*)part, U, V, b, H, dU, db, lossp);
+  VS_LAUNCH_CHECK();
+  if (grad) {
+    hipLaunchKernelGGL(rrr_dv_kernel, dim3((unsigned)T), dim3(256), 0, s, T, N, (int)C, (int)r, U, (const double*)H, dV);
+    VS_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(rrr_loss_kernel, dim3(1), dim3(256), 0, s, (int64_t)(C + 2) * N, (const double*)lossp, loss);
+  VS_LAUNCH_CHECK();
+  return VS_OK;
+}
+
+extern "C" size_t vs_rrr_score_workspace_bytes(int64_t K, int64_t N) {
+  if (K <= 0 || N <= 0) return 0;
+  return score_ws(K, N).total;
+}
+
+extern "C" int vs_rrr_score(int64_t K, int64_t T, int64_t N, int64_t C, int64_t r, const double* X, const double* U,
+                            const double* V, const double* b, const double* mean_y, const double* std_y,
+                            const void* gt, int32_t gt_dtype, double* pred, double* bps, double* r2, double* out,
+                            void* workspace, void* stream) {
+  VS_REQUIRE(C >= 1 && C <= kRrrMaxC, "vs_rrr_score: 1 <= C <= 32 features (without the bias column)");
+  VS_REQUIRE(r >= 1 && r <= kRrrMaxR, "vs_rrr_score: 1 <= r <= 8 components");
+  VS_REQUIRE(rrr_dims_ok(K, T, N, C, r), "vs_rrr_score: K, T, N must be positive (T <= 65535)");
+  VS_REQUIRE(gt_dtype == VS_F32 || gt_dtype == VS_F64, "vs_rrr_score: gt must be f32 or f64");
+  VS_REQUIRE(X && U && V && b && mean_y && std_y && gt && bps && r2 && out && workspace,
+             "vs_rrr_score: null pointer");
+  VS_REQUIRE((((uintptr_t)workspace) & 15u) == 0, "vs_rrr_score: workspace must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const ScoreWs w = score_ws(K, N);
+  double* stat = (double*)workspace;
+  ScopedTimer timer(VS_TIMER_MISC, s,
+                    (double)K * T * ((double)N * ((gt_dtype == VS_F32 ? 4.0 : 8.0) + (pred ? 8.0 : 0.0)) + (C + 1) * 8.0));
+  const dim3 grid((unsigned)cdiv(N, 64), (unsigned)w.chunks);
+  if (gt_dtype == VS_F32)
+    hipLaunchKernelGGL(rrr_score_kernel<float>, grid, dim3(256), 0, s, K, T, N, (int)C, (int)r, w.kchunk, X, U, V, b,
+                       mean_y, std_y, (const float*)gt, pred, stat);
+  else
+    hipLaunchKernelGGL(rrr_score_kernel<double>, grid, dim3(256), 0, s, K, T, N, (int)C, (int)r, w.kchunk, X, U, V, b,
+                       mean_y, std_y, (const double*)gt, pred, stat);
+  VS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rrr_score_final_kernel, dim3(1), dim3(256), 0, s, K, T, N, w.chunks, (const double*)stat, bps, r2,
+                     out);
+  VS_LAUNCH_CHECK();
+  return VS_OK;
+}

@@ -13,7 +13,7 @@ import torch
 
 from .build import LIB_PATH
 
-VS_F32, VS_BF16, VS_U8, VS_FP8 = 0, 1, 2, 3
+VS_F32, VS_BF16, VS_U8, VS_FP8, VS_F64 = 0, 1, 2, 3, 4
 EPI_BIAS, EPI_GELU, EPI_RELU, EPI_RESIDUAL, EPI_POS = 0x1, 0x2, 0x4, 0x8, 0x10
 EPI_GELU_BWD, EPI_RELU_BWD, EPI_ATOMIC, EPI_ACCUM = 0x20, 0x40, 0x80, 0x100
 EPI_GELU_GRAD, EPI_MUL_AUX = 0x200, 0x400
@@ -51,6 +51,7 @@ KNOB_COUNT = 40
 
 c_i32, c_i64, c_u32, c_f32, c_p, c_sz = (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float,
                                          ctypes.c_void_p, ctypes.c_size_t)
+c_f64 = ctypes.c_double
 
 
 class VsError(RuntimeError):
@@ -200,6 +201,12 @@ PROTOTYPES = {
                                          c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "vs_info_nce_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vs_info_nce": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f32, c_p, c_p, c_p]),
+    "vs_rrr_loss_grad_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "vs_rrr_loss_grad": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i32, c_p, c_p, c_p, c_f64, c_p,
+                                        c_p, c_p, c_p, c_p, c_p]),
+    "vs_rrr_score_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "vs_rrr_score": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_p,
+                                    c_p, c_p, c_p, c_p, c_p]),
     "vs_timing_enable": (ctypes.c_int, [ctypes.c_int]),
     "vs_timing_collect": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double)]),
     "vs_timing_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),

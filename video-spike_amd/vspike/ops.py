@@ -427,6 +427,76 @@ def info_nce(ref, pos, neg, out, log_inv_tau=None, d_ref=None, d_pos=None, d_neg
     return out
 
 
+def _rrr_dims(X, y, U, V, b, what):
+    """(K, T, N, C, r) of the RRR operands after checking them: X [K, T, C+1] f64, y [K, T, N] f32 / f64,
+    U [N, C, r], V [r, T], b [N, 1, T] f64, all dense."""
+    K, T, C1 = X.shape
+    N, C, r = U.shape
+    ok = (C1 == C + 1 and tuple(y.shape) == (K, T, N) and tuple(V.shape) == (r, T) and b.numel() == N * T
+          and y.dtype in (torch.float32, torch.float64)
+          and all(t.dtype == torch.float64 for t in (X, U, V, b))
+          and all(t.is_contiguous() for t in (X, y, U, V, b)))
+    if not ok:
+        raise L.VsError(f"{what}: X [K, T, C+1], U [N, C, r], V [r, T], b [N, 1, T] dense float64 and "
+                        "y [K, T, N] dense float32 / float64")
+    return K, T, N, C, r
+
+
+def _f64_code(t):
+    return L.VS_F64 if t.dtype == torch.float64 else L.VS_F32
+
+
+def rrr_loss_grad_workspace_bytes(K, T, N, C):
+    return int(lib().vs_rrr_loss_grad_workspace_bytes(K, T, N, C))
+
+
+def rrr_loss_grad(X, y, U, V, b, l2, loss, dU=None, dV=None, db=None, workspace=None):
+    """The RRR loss sum (yhat - y)^2 + l2 sum beta^2 into `loss` (f64[1]) and, when dU / dV / db are given
+    (together), its gradients (vs_rrr_loss_grad).  1 <= C <= 32, 1 <= r <= 8."""
+    require_device(X, y, U, V, b, loss, dU, dV, db, workspace)
+    K, T, N, C, r = _rrr_dims(X, y, U, V, b, "rrr_loss_grad")
+    for g, ref in ((dU, U), (dV, V), (db, b)):
+        if g is not None and (g.numel() != ref.numel() or g.dtype != torch.float64 or not g.is_contiguous()):
+            raise L.VsError("rrr_loss_grad: dU / dV / db are dense float64 of the shapes of U / V / b")
+    if loss.dtype != torch.float64 or loss.numel() < 1:
+        raise L.VsError("rrr_loss_grad: loss must hold one float64")
+    need = rrr_loss_grad_workspace_bytes(K, T, N, C) if 1 <= C <= 32 else 0
+    if workspace is None:
+        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise L.VsError("rrr_loss_grad: workspace too small")
+    check(lib().vs_rrr_loss_grad(K, T, N, C, r, X.data_ptr(), y.data_ptr(), _f64_code(y), U.data_ptr(), V.data_ptr(),
+                                 b.data_ptr(), float(l2), loss.data_ptr(), ptr(dU), ptr(dV), ptr(db),
+                                 workspace.data_ptr(), stream()), "vs_rrr_loss_grad")
+    return loss
+
+
+def rrr_score_workspace_bytes(K, N):
+    return int(lib().vs_rrr_score_workspace_bytes(K, N))
+
+
+def rrr_score(X, U, V, b, mean_y, std_y, gt, bps, r2, out, pred=None, workspace=None):
+    """train_rrr's scoring on the held-out trials (vs_rrr_score): pred = max(yhat std_y + mean_y, 1e-3)
+    (written when `pred` [K, T, N] f64 is given), per-neuron bits per spike `bps` [N] and trial-mean R^2 `r2`
+    [N], and out f64[2] = their NaN-ignoring means over neurons (co_bps, mean R^2)."""
+    require_device(X, U, V, b, mean_y, std_y, gt, bps, r2, out, pred, workspace)
+    K, T, N, C, r = _rrr_dims(X, gt, U, V, b, "rrr_score")
+    for t, numel in ((mean_y, T * N), (std_y, T * N), (bps, N), (r2, N), (pred, K * T * N)):
+        if t is not None and (t.numel() != numel or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise L.VsError("rrr_score: mean_y / std_y [T, N], bps / r2 [N], pred [K, T, N] dense float64")
+    if out.dtype != torch.float64 or out.numel() < 2:
+        raise L.VsError("rrr_score: out must hold two float64")
+    need = rrr_score_workspace_bytes(K, N)
+    if workspace is None:
+        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise L.VsError("rrr_score: workspace too small")
+    check(lib().vs_rrr_score(K, T, N, C, r, X.data_ptr(), U.data_ptr(), V.data_ptr(), b.data_ptr(), mean_y.data_ptr(),
+                             std_y.data_ptr(), gt.data_ptr(), _f64_code(gt), ptr(pred), bps.data_ptr(), r2.data_ptr(),
+                             out.data_ptr(), workspace.data_ptr(), stream()), "vs_rrr_score")
+    return out
+
+
 def poisson_nll(log_rate, target, loss_out, dx=None, grad_scale=1.0, workspace=None):
     require_device(log_rate, target, loss_out)
     n = log_rate.numel()

@@ -96,6 +96,36 @@ class ContrastTrainer:
             self.model.train(was_training)
         return torch.cat(zs, dim=0)
 
+    @torch.no_grad()
+    def validate(self, train_batches: Iterable, val_batches: Iterable, idx=None, eid: str = "session") -> dict:
+        """`src/trainer/contrast.py:129-162`: embed every frame of the train and validation trials in eval mode,
+        fit the reduced-rank regression from the embeddings to the binned spikes and score the held-out trials
+        (vspike.rrr.train_rrr); returns {'val_bps': nanmean of the per-neuron bits per spike}, the number the
+        reference keeps its best checkpoint by.  Batches are dicts with the frames under 'ref' ((F, C, H, W),
+        or 5-D with a leading 1, contrast.py:188-189) and the spikes (trials, T, N) under 'neural'.
+        idx: the T frames regressed on; default the reference's draw from numpy's global generator,
+        sort(choice(F - 1, T, replace=False)) (at F = 120, T = 100 its `choice(119, 100)`, last frame never used).
+        The embeddings stay on the device between the transform and the fit."""
+        import numpy as np
+        from .rrr import train_rrr
+        X, y = [], []
+        for batches in (train_batches, val_batches):
+            batches = list(batches)
+            frames = [b["ref"].squeeze(0) if b["ref"].dim() == 5 else b["ref"] for b in batches]
+            z = self.transform(frames)
+            neural = torch.cat([b["neural"] for b in batches], dim=0).to(z.device)
+            X.append(z.view(neural.shape[0], -1, z.shape[-1]))
+            y.append(neural)
+        F, T = X[0].shape[1], y[0].shape[1]
+        if idx is None:
+            idx = np.sort(np.random.choice(F - 1, T, replace=False))
+        sel = torch.as_tensor(np.asarray(idx), dtype=torch.long, device=X[0].device)
+        if sel.numel() != T:
+            raise ValueError(f"ContrastTrainer.validate: {sel.numel()} frame indices for {T} time bins")
+        data = {eid: {"X": [x[:, sel, :] for x in X], "y": y, "setup": {}}}
+        res = train_rrr(data)
+        return {"val_bps": float(np.nanmean(res[eid]["bps"]))}
+
 
 class Trainer:
     def __init__(self, model, optimizer, lr_scheduler=None, config=None, criterion=None,
