@@ -71,7 +71,10 @@ int vs_struct_size(int which);
 #define VS_EPI_RELU_BWD  0x040u  /* v = aux_in(m,n) > 0 ? v : 0                                */
 #define VS_EPI_ATOMIC    0x080u  /* C(m,n) += v (split-K); C must be f32.  With a workspace the  */
                                  /* splits are summed in a fixed order (no atomics); with RELU  */
-                                 /* (skinny path only) C = relu(C + v)                          */
+                                 /* (skinny path only) C = relu(C + v).  alpha scales v, never   */
+                                 /* the bias or the old C; the skinny and dW kernels take alpha */
+                                 /* 1 only (another alpha runs on the generic split-K tiles),   */
+                                 /* so ATOMIC|RELU with alpha != 1 is rejected (VS_EINVAL)      */
 #define VS_EPI_ACCUM     0x100u  /* C(m,n) += v (plain read-modify-write); C must be f32      */
 #define VS_EPI_GELU_GRAD 0x200u  /* with VS_EPI_GELU: aux_out(m,n) = gelu'(v) instead of v: the  */
                                  /* factor the backward multiplies by (bf16 ViT path: the fc1    */
@@ -687,6 +690,12 @@ int vs_timing_bytes(int timer, double* algorithmic_bytes);   /* call before vs_t
 /* copies min(n, VS_PATH_COUNT) counters into out; returns VS_PATH_COUNT */
 int vs_dispatch_counts(int64_t* out, int n);
 int vs_dispatch_reset(void);
+/* The LayerNorm kernel instantiations, counted the same way (vs_dispatch_reset zeroes them too): kernel
+   ids 0..5 = the scalar kernels with 2, 3, 4, 8, 12, 16 values per lane (cols <= 128, 192, 256, 512, 768,
+   1024), ids 6..8 = the vectorised kernels of cols 192, 384, 768.  out[k] = forward launches of kernel k,
+   out[VS_LN_KERNELS + k] = backward launches.  Copies min(n, 2 * VS_LN_KERNELS); returns 2 * VS_LN_KERNELS. */
+#define VS_LN_KERNELS 9
+int vs_ln_dispatch_counts(int64_t* out, int n);
 /* 1 when every compiled instance of the 256 x 256 forward / dX GEMM (VS_PATH_GEMM_G256) has no private
    (scratch) segment: its early-DMA wait counts the epilogue's stores exactly.  An instance that spills
    falls back to vmcnt(0) on its own; this is the test's view of the same check. */

@@ -45,6 +45,8 @@ void set_error(const char* msg);
 int knob(int id);
 // dispatch counters (VS_PATH_*): one relaxed host-side add per launch of a path
 void count_path(int id);
+// LayerNorm kernel counters (vs_ln_dispatch_counts): kernel 0..VS_LN_KERNELS-1, forward or backward
+void count_ln(int kernel, bool bwd);
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

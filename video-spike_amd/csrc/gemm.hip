@@ -2984,7 +2984,7 @@ static bool vec_ok(const vs_gemm_desc* d) {
   if (f & VS_EPI_BIAS) ok = ok && aligned16(d->bias);
   if (f & VS_EPI_POS) ok = ok && aligned16(d->pos) && d->N % 4 == 0;
   if (f & VS_EPI_RESIDUAL) ok = ok && aligned16(d->residual) && d->ld_residual % 4 == 0;
-  if (f & (VS_EPI_GELU_BWD | VS_EPI_RELU_BWD)) ok = ok && aligned16(d->aux_in) && d->ld_aux_in % avec == 0;
+  if (f & (VS_EPI_GELU_BWD | VS_EPI_RELU_BWD | VS_EPI_MUL_AUX)) ok = ok && aligned16(d->aux_in) && d->ld_aux_in % avec == 0;
   if (f & VS_EPI_GELU) ok = ok && aligned16(d->aux_out) && d->ld_aux_out % avec == 0;
   return ok;
 }
@@ -3036,7 +3036,7 @@ extern "C" int vs_gemm(const vs_gemm_desc* d, void* stream) {
   VS_REQUIRE(!(f & VS_EPI_BIAS) || d->bias, "vs_gemm: BIAS needs bias");
   VS_REQUIRE(!(f & VS_EPI_RESIDUAL) || d->residual, "vs_gemm: RESIDUAL needs residual");
   VS_REQUIRE(!(f & VS_EPI_POS) || (d->pos && d->pos_rows > 0), "vs_gemm: POS needs pos/pos_rows");
-  VS_REQUIRE(!(f & (VS_EPI_GELU_BWD | VS_EPI_RELU_BWD)) || d->aux_in, "vs_gemm: *_BWD needs aux_in");
+  VS_REQUIRE(!(f & (VS_EPI_GELU_BWD | VS_EPI_RELU_BWD | VS_EPI_MUL_AUX)) || d->aux_in, "vs_gemm: *_BWD / MUL_AUX need aux_in");
   VS_REQUIRE(!(f & VS_EPI_GELU) || d->aux_out, "vs_gemm: GELU needs aux_out");
   VS_REQUIRE(!(f & (VS_EPI_ATOMIC | VS_EPI_ACCUM)) || d->out_dtype == VS_F32, "vs_gemm: ATOMIC/ACCUM need f32 C");
   VS_REQUIRE(!((f & VS_EPI_ATOMIC) && (f & ~(VS_EPI_ATOMIC | VS_EPI_BIAS | VS_EPI_RELU))),
@@ -3063,7 +3063,10 @@ extern "C" int vs_gemm(const vs_gemm_desc* d, void* stream) {
   // token-reduction weight gradients (dW = dY^T X, both operands token-major): the long-K products
   // with 256-multiple widths on the 256 x 256 persistent kernel, the rest on the split-K dW kernel
   // (gemm_dw.hip); both reduce their partials in a fixed order
-  if (!knob(VS_KNOB_NO_DW256) && d->dtype == VS_BF16 && d->out_dtype == VS_F32 && f == VS_EPI_ATOMIC &&
+  // (none of the three kernels below scales by alpha: alpha != 1 takes the generic split-K tiles, whose
+  // store_tile multiplies every split's partial tile)
+  const bool unit_alpha = d->alpha == 1.0f;
+  if (!knob(VS_KNOB_NO_DW256) && unit_alpha && d->dtype == VS_BF16 && d->out_dtype == VS_F32 && f == VS_EPI_ATOMIC &&
       !d->a_kcontig && !d->b_kcontig && d->split_k <= 0 && use_ws && d->lda % 8 == 0 && d->ldb % 8 == 0 &&
       d->ldc % 4 == 0 && aligned16(d->c) && 64 * d->lda * 2 < (1ll << 31) && 64 * d->ldb * 2 < (1ll << 31)) {
     const Dw256Plan p = plan_dw256(d->M, d->N, d->K);
@@ -3085,16 +3088,16 @@ extern "C" int vs_gemm(const vs_gemm_desc* d, void* stream) {
       return VS_OK;
     }
   }
-  if (!knob(VS_KNOB_DW_OLD) && d->dtype == VS_BF16 && d->out_dtype == VS_F32 && f == VS_EPI_ATOMIC && !d->a_kcontig &&
+  if (!knob(VS_KNOB_DW_OLD) && unit_alpha && d->dtype == VS_BF16 && d->out_dtype == VS_F32 && f == VS_EPI_ATOMIC && !d->a_kcontig &&
       !d->b_kcontig && d->split_k <= 0 && use_ws && d->K >= 1 && d->M % 8 == 0 && d->N % 8 == 0 &&
       d->lda % 8 == 0 && d->ldb % 8 == 0 && (size_t)d->workspace_bytes >= dw_workspace_bytes(d->M, d->N, d->K))
     return count_path(VS_PATH_GEMM_DW), launch_dw(d, s);
   // skinny split-K with K-contiguous operands (the head forward): fragments straight from HBM
   const bool dense_c = d->ldc == d->N && aligned16(d->c) && (!(f & VS_EPI_BIAS) || aligned16(d->bias));
-  const bool skinny = !knob(VS_KNOB_NO_SKINNY) && use_ws && dense_c && skinny_ok(d) &&
+  const bool skinny = !knob(VS_KNOB_NO_SKINNY) && unit_alpha && use_ws && dense_c && skinny_ok(d) &&
                       (size_t)d->workspace_bytes >= skinny_workspace_bytes(d->dtype, d->M, d->N, d->K);
   VS_REQUIRE(skinny || !((f & VS_EPI_ATOMIC) && (f & VS_EPI_RELU)),
-             "vs_gemm: ATOMIC|RELU needs the skinny split-K path (M <= 64, N <= 256, K-contiguous, workspace)");
+             "vs_gemm: ATOMIC|RELU needs the skinny split-K path (M <= 64, N <= 256, K-contiguous, workspace, alpha 1)");
   if (skinny) {
     int S = 0;
     count_path(VS_PATH_GEMM_SKINNY);

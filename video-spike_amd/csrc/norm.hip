@@ -415,15 +415,16 @@ static void launch_bwd(int64_t rows, int64_t cols, const TD* dy, int64_t lddy, c
 
 using namespace vs;
 
-#define VS_LN_DISPATCH(CALL)              \
-  do {                                    \
-    const int64_t vpl = cdiv(cols, 64);   \
-    if (vpl <= 2) CALL(2);                \
-    else if (vpl <= 3) CALL(3);           \
-    else if (vpl <= 4) CALL(4);           \
-    else if (vpl <= 8) CALL(8);           \
-    else if (vpl <= 12) CALL(12);         \
-    else CALL(16);                        \
+// (count_ln ids: 0..5 = these six scalar instantiations, 6..8 = the vectorised LPR 16 / 32 / 64)
+#define VS_LN_DISPATCH(CALL, BWD)                      \
+  do {                                                 \
+    const int64_t vpl = cdiv(cols, 64);                \
+    if (vpl <= 2) { count_ln(0, BWD); CALL(2); }       \
+    else if (vpl <= 3) { count_ln(1, BWD); CALL(3); }  \
+    else if (vpl <= 4) { count_ln(2, BWD); CALL(4); }  \
+    else if (vpl <= 8) { count_ln(3, BWD); CALL(8); }  \
+    else if (vpl <= 12) { count_ln(4, BWD); CALL(12); } \
+    else { count_ln(5, BWD); CALL(16); }               \
   } while (0)
 
 extern "C" int vs_layernorm_fwd(int32_t y_dtype, int64_t rows, int64_t cols, const float* x, int64_t ldx,
@@ -452,16 +453,17 @@ extern "C" int vs_layernorm_fwd(int32_t y_dtype, int64_t rows, int64_t cols, con
       if (lpr == 16) FV_(float, 16); else if (lpr == 32) FV_(float, 32); else FV_(float, 64);
     }
 #undef FV_
+    count_ln(lpr == 16 ? 6 : lpr == 32 ? 7 : 8, false);
     VS_LAUNCH_CHECK();
     return VS_OK;
   }
   if (y_dtype == VS_BF16) {
 #define F_(V) launch_fwd<bf16_t, V>(rows, cols, x, ldx, gamma, beta, eps, y, ldy, mean, rstd, s)
-    VS_LN_DISPATCH(F_);
+    VS_LN_DISPATCH(F_, false);
 #undef F_
   } else {
 #define F_(V) launch_fwd<float, V>(rows, cols, x, ldx, gamma, beta, eps, y, ldy, mean, rstd, s)
-    VS_LN_DISPATCH(F_);
+    VS_LN_DISPATCH(F_, false);
 #undef F_
   }
   VS_LAUNCH_CHECK();
@@ -506,6 +508,7 @@ static int layernorm_bwd_t(int64_t rows, int64_t cols, const TD* dy, int64_t ldd
                      dres, lddres, dx, lddx, (bf16_t*)dx_lp, dgamma, dbeta, part, rows)
     if (lpr == 16) BV_(16); else if (lpr == 32) BV_(32); else BV_(64);
 #undef BV_
+    count_ln(lpr == 16 ? 6 : lpr == 32 ? 7 : 8, true);
     if (part)
       hipLaunchKernelGGL(ln_partsum_kernel, dim3((unsigned)cdiv(2 * cols, 16)), dim3(1024), 0, s, part, (int)grid,
                          (int)cols, dgamma, dbeta);
@@ -514,7 +517,7 @@ static int layernorm_bwd_t(int64_t rows, int64_t cols, const TD* dy, int64_t ldd
   }
 #define B_(V) launch_bwd<V, TD>(rows, cols, dy, lddy, x, ldx, mean, rstd, gamma, dres, lddres, dx, lddx, dx_lp, dgamma, \
                                 dbeta, (float*)workspace, s)
-  VS_LN_DISPATCH(B_);
+  VS_LN_DISPATCH(B_, true);
 #undef B_
   VS_LAUNCH_CHECK();
   return VS_OK;

@@ -55,6 +55,10 @@ int knob(int id) {
 
 static std::atomic<int64_t> g_dispatch[VS_PATH_COUNT];
 void count_path(int id) { g_dispatch[id].fetch_add(1, std::memory_order_relaxed); }
+static std::atomic<int64_t> g_ln_dispatch[2 * VS_LN_KERNELS];
+void count_ln(int kernel, bool bwd) {
+  g_ln_dispatch[(bwd ? VS_LN_KERNELS : 0) + kernel].fetch_add(1, std::memory_order_relaxed);
+}
 
 // Event pairs recorded around tracked launches while timing is enabled.  Events are pooled and
 // only read back in vs_timing_collect(), so recording never synchronises the stream.
@@ -126,7 +130,12 @@ extern "C" int vs_dispatch_counts(int64_t* out, int n) {
 }
 extern "C" int vs_dispatch_reset(void) {
   for (auto& c : vs::g_dispatch) c.store(0, std::memory_order_relaxed);
+  for (auto& c : vs::g_ln_dispatch) c.store(0, std::memory_order_relaxed);
   return VS_OK;
+}
+extern "C" int vs_ln_dispatch_counts(int64_t* out, int n) {
+  for (int i = 0; i < n && i < 2 * VS_LN_KERNELS; ++i) out[i] = vs::g_ln_dispatch[i].load(std::memory_order_relaxed);
+  return 2 * VS_LN_KERNELS;
 }
 
 extern "C" int vs_struct_size(int which) {

@@ -105,6 +105,7 @@ PROTOTYPES = {
     "vs_build_id": (ctypes.c_char_p, []),
     "vs_dispatch_counts": (ctypes.c_int, [ctypes.POINTER(c_i64), ctypes.c_int]),
     "vs_dispatch_reset": (ctypes.c_int, []),
+    "vs_ln_dispatch_counts": (ctypes.c_int, [ctypes.POINTER(c_i64), ctypes.c_int]),
     "vs_g256_scratch_free": (ctypes.c_int, []),
     "vs_knob_get": (ctypes.c_int, [ctypes.c_int]),
     "vs_knob_set": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
@@ -297,6 +298,22 @@ def dispatch_counts() -> dict:
     total = lib().vs_dispatch_counts(buf, len(names))
     if total != len(names):
         raise VsError(f"dispatch counters: the library has {total}, the binding names {len(names)}")
+    return {name: int(buf[i]) for i, name in enumerate(names)}
+
+
+# vs_ln_dispatch_counts' kernel ids (vspike.h): the scalar instantiations by values per lane, then the vectorised widths
+LN_KERNEL_NAMES = ("vpl2", "vpl3", "vpl4", "vpl8", "vpl12", "vpl16", "vec192", "vec384", "vec768")
+
+
+def ln_dispatch_counts() -> dict:
+    """LayerNorm launches per kernel instantiation since the last dispatch_reset(): {"fwd_vpl2": n, ...,
+    "bwd_vec768": n} (vs_ln_dispatch_counts)."""
+    n = 2 * len(LN_KERNEL_NAMES)
+    buf = (c_i64 * n)()
+    total = lib().vs_ln_dispatch_counts(buf, n)
+    if total != n:
+        raise VsError(f"LayerNorm counters: the library has {total}, the binding names {n}")
+    names = [f"{d}_{k}" for d in ("fwd", "bwd") for k in LN_KERNEL_NAMES]
     return {name: int(buf[i]) for i, name in enumerate(names)}
 
 
