@@ -590,6 +590,33 @@ int vs_rrr_score(int64_t K, int64_t T, int64_t N, int64_t C, int64_t r, const do
                  int32_t gt_dtype, double* pred, double* bps, double* r2, double* out, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The RRR baseline (src/train_rrr.py) on wide inputs (csrc/rrr_wide.hip): the same
+ * operands, results and contracts as vs_rrr_loss_grad / vs_rrr_score for 1 <= C <= 1024 (C <= 32 included, so
+ * both can run on the same inputs) and 1 <= r <= 8, else VS_EINVAL before any launch.  Per time bin the two
+ * products yhat = X beta and G = X^T 2 res run on the f64 MFMA; beta is never stored.  All f64, no atomics,
+ * bitwise repeatable.
+ * ------------------------------------------------------------------------------------------ */
+/* workspace (doubles, each piece rounded up to 256 bytes): K T N (residuals) + T (C+2) N (G, then H in place)
+   + (C+2) ceil(N/64) (loss terms) + min(C, 32) 8 T (dV partials); 0.48 GB at K 400, T 100, N 512, C 768 */
+size_t vs_rrr_wide_loss_grad_workspace_bytes(int64_t K, int64_t T, int64_t N, int64_t C);
+int vs_rrr_wide_loss_grad(int64_t K, int64_t T, int64_t N, int64_t C, int64_t r, const double* X, const void* y,
+                          int32_t y_dtype, const double* U, const double* V, const double* b, double l2,
+                          double* loss, double* dU, double* dV, double* db, void* workspace, void* stream);
+/* workspace: K T N doubles (the standardised yhat) + the statistics of vs_rrr_score */
+size_t vs_rrr_wide_score_workspace_bytes(int64_t K, int64_t T, int64_t N);
+int vs_rrr_wide_score(int64_t K, int64_t T, int64_t N, int64_t C, int64_t r, const double* X, const double* U,
+                      const double* V, const double* b, const double* mean_y, const double* std_y, const void* gt,
+                      int32_t gt_dtype, double* pred, double* bps, double* r2, double* out, void* workspace,
+                      void* stream);
+/* out = scipy.ndimage.gaussian_filter1d(y, sigma, axis=1) (mode 'reflect') for y [K, T, N], VS_F32 or VS_F64,
+   bit for bit: weights = device f64[2 radius + 1], the normalised kernel the caller computes as scipy does
+   (radius = int(4 sigma + 0.5), exp(-0.5 / sigma^2 x^2) / sum).  Each output is accumulated in f64 in scipy's
+   order (centre tap, then the pairs from the outermost in; product and sum rounded separately) and rounded
+   once to y's dtype.  T >= radius + 1 (a single reflection), out must not alias y. */
+int vs_gauss_smooth_time(int64_t K, int64_t T, int64_t N, const void* y, int32_t dtype, const double* weights,
+                         int64_t radius, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Trial shards (host side of the input path; replaces the per-trial webdataset tars of
  * src/prepare_data.py:210-235 read by src/loader/base.py:21-41).  Fixed-size records: raw uint8
  * frames (T, C, H, W) + f32 spike counts (ap_rows, ap_cols) + a 64-byte "<eid>_<trial>" key.
@@ -622,7 +649,7 @@ const char* vs_shard_last_error(void);
 #define VS_TIMER_LN_FWD   4   /* vs_layernorm_fwd */
 #define VS_TIMER_LN_BWD   5   /* vs_layernorm_bwd (+ its partial-sum reduction) */
 #define VS_TIMER_ADAMW    6   /* vs_adamw */
-#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd), vs_token_pool_*, vs_cls_embed_*, vs_embed_head_*, vs_info_nce, vs_rrr_* */
+#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd), vs_token_pool_*, vs_cls_embed_*, vs_embed_head_*, vs_info_nce, vs_rrr_*, vs_gauss_smooth_time */
 /* per-product tags of the ViT block executor (vs_vit_layer_fwd / _bwd): its vs_gemm calls are
    charged to these instead of VS_TIMER_GEMM / VS_TIMER_GEMM_DW, so every product has its own timer */
 #define VS_TIMER_FWD_QKV   8   /* qkv = h1 Wqkv^T + b          (mv:233-236) */
@@ -696,6 +723,12 @@ int vs_dispatch_reset(void);
    out[VS_LN_KERNELS + k] = backward launches.  Copies min(n, 2 * VS_LN_KERNELS); returns 2 * VS_LN_KERNELS. */
 #define VS_LN_KERNELS 9
 int vs_ln_dispatch_counts(int64_t* out, int n);
+/* The RRR baseline's counters, counted the same way (vs_dispatch_reset zeroes them too).  They are a group of
+   their own because VS_PATH_COUNT is pinned at 30 by a test of the contrastive path. */
+#define VS_RRR_PATH_WIDE   0   /* vs_rrr_wide_loss_grad / vs_rrr_wide_score: one per call */
+#define VS_RRR_PATH_SMOOTH 1   /* vs_gauss_smooth_time: one per call */
+#define VS_RRR_PATH_COUNT  2
+int vs_rrr_dispatch_counts(int64_t* out, int n);
 /* 1 when every compiled instance of the 256 x 256 forward / dX GEMM (VS_PATH_GEMM_G256) has no private
    (scratch) segment: its early-DMA wait counts the epilogue's stores exactly.  An instance that spills
    falls back to vmcnt(0) on its own; this is the test's view of the same check. */

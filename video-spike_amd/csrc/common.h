@@ -47,6 +47,8 @@ int knob(int id);
 void count_path(int id);
 // LayerNorm kernel counters (vs_ln_dispatch_counts): kernel 0..VS_LN_KERNELS-1, forward or backward
 void count_ln(int kernel, bool bwd);
+// RRR baseline counters (VS_RRR_PATH_*, vs_rrr_dispatch_counts)
+void count_rrr(int id);
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

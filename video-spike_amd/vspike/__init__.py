@@ -10,7 +10,7 @@ from .linear import Linear
 from .loss import InfoNCE, MSEMeanLoss, PoissonNLLMeanLoss, make_criterion, mse_mean, poisson_nll_mean
 from .optim import FusedAdamW
 from .r3d import R3D
-from .rrr import RRR, train_rrr
+from .rrr import RRR, RRRGD, prepare_rrr_inputs, train_rrr, train_rrr_baseline
 from .temporal import VideoMAETemporal
 from .vit import VideoMAE
 
@@ -25,6 +25,6 @@ NAME2MODEL = {
     "ContrastViT": ContrastViT,
 }
 
-__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "ContrastViT", "InfoNCE", "RRR", "train_rrr", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
+__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "ContrastViT", "InfoNCE", "RRR", "train_rrr", "RRRGD", "prepare_rrr_inputs", "train_rrr_baseline", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
            "mse_mean", "MSEMeanLoss", "make_criterion",
            "DictConfig", "update_config", "config_from_kwargs", "load_run_config"]

@@ -208,6 +208,14 @@ PROTOTYPES = {
     "vs_rrr_score_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vs_rrr_score": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_p,
                                     c_p, c_p, c_p, c_p, c_p]),
+    "vs_rrr_wide_loss_grad_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "vs_rrr_wide_loss_grad": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i32, c_p, c_p, c_p, c_f64,
+                                             c_p, c_p, c_p, c_p, c_p, c_p]),
+    "vs_rrr_wide_score_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "vs_rrr_wide_score": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32,
+                                         c_p, c_p, c_p, c_p, c_p, c_p]),
+    "vs_gauss_smooth_time": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_i32, c_p, c_i64, c_p, c_p]),
+    "vs_rrr_dispatch_counts": (ctypes.c_int, [ctypes.POINTER(c_i64), ctypes.c_int]),
     "vs_timing_enable": (ctypes.c_int, [ctypes.c_int]),
     "vs_timing_collect": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double)]),
     "vs_timing_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
@@ -315,6 +323,21 @@ def ln_dispatch_counts() -> dict:
         raise VsError(f"LayerNorm counters: the library has {total}, the binding names {n}")
     names = [f"{d}_{k}" for d in ("fwd", "bwd") for k in LN_KERNEL_NAMES]
     return {name: int(buf[i]) for i, name in enumerate(names)}
+
+
+# vs_rrr_dispatch_counts' ids (vspike.h VS_RRR_PATH_*): a group of their own, like the LayerNorm counters, because
+# a test of the contrastive path pins vs_dispatch_counts' total at PATH_COUNT + len(CONTRAST_PATH_NAMES)
+RRR_PATH_NAMES = ("rrr_wide", "gauss_smooth")
+
+
+def rrr_dispatch_counts() -> dict:
+    """Calls per RRR-baseline path since the last dispatch_reset(): {"rrr_wide": n, "gauss_smooth": n}."""
+    n = len(RRR_PATH_NAMES)
+    buf = (c_i64 * n)()
+    total = lib().vs_rrr_dispatch_counts(buf, n)
+    if total != n:
+        raise VsError(f"RRR counters: the library has {total}, the binding names {n}")
+    return {name: int(buf[i]) for i, name in enumerate(RRR_PATH_NAMES)}
 
 
 def total_path_count() -> int:

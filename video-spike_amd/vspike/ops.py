@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes
 import math
 
+import numpy as np
+
 import torch
 
 from . import _lib as L
@@ -494,6 +496,88 @@ def rrr_score(X, U, V, b, mean_y, std_y, gt, bps, r2, out, pred=None, workspace=
     check(lib().vs_rrr_score(K, T, N, C, r, X.data_ptr(), U.data_ptr(), V.data_ptr(), b.data_ptr(), mean_y.data_ptr(),
                              std_y.data_ptr(), gt.data_ptr(), _f64_code(gt), ptr(pred), bps.data_ptr(), r2.data_ptr(),
                              out.data_ptr(), workspace.data_ptr(), stream()), "vs_rrr_score")
+    return out
+
+
+def rrr_wide_loss_grad_workspace_bytes(K, T, N, C):
+    return int(lib().vs_rrr_wide_loss_grad_workspace_bytes(K, T, N, C))
+
+
+def rrr_wide_loss_grad(X, y, U, V, b, l2, loss, dU=None, dV=None, db=None, workspace=None):
+    """rrr_loss_grad for 1 <= C <= 1024 features (vs_rrr_wide_loss_grad: the two products per time bin on the
+    float64 MFMA).  The same operands, results and checks; 1 <= r <= 8."""
+    require_device(X, y, U, V, b, loss, dU, dV, db, workspace)
+    K, T, N, C, r = _rrr_dims(X, y, U, V, b, "rrr_wide_loss_grad")
+    for g, ref in ((dU, U), (dV, V), (db, b)):
+        if g is not None and (g.numel() != ref.numel() or g.dtype != torch.float64 or not g.is_contiguous()):
+            raise L.VsError("rrr_wide_loss_grad: dU / dV / db are dense float64 of the shapes of U / V / b")
+    if loss.dtype != torch.float64 or loss.numel() < 1:
+        raise L.VsError("rrr_wide_loss_grad: loss must hold one float64")
+    need = rrr_wide_loss_grad_workspace_bytes(K, T, N, C) if 1 <= C <= 1024 else 0
+    if workspace is None:
+        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise L.VsError("rrr_wide_loss_grad: workspace too small")
+    check(lib().vs_rrr_wide_loss_grad(K, T, N, C, r, X.data_ptr(), y.data_ptr(), _f64_code(y), U.data_ptr(),
+                                      V.data_ptr(), b.data_ptr(), float(l2), loss.data_ptr(), ptr(dU), ptr(dV),
+                                      ptr(db), workspace.data_ptr(), stream()), "vs_rrr_wide_loss_grad")
+    return loss
+
+
+def rrr_wide_score_workspace_bytes(K, T, N):
+    return int(lib().vs_rrr_wide_score_workspace_bytes(K, T, N))
+
+
+def rrr_wide_score(X, U, V, b, mean_y, std_y, gt, bps, r2, out, pred=None, workspace=None):
+    """rrr_score for 1 <= C <= 1024 features (vs_rrr_wide_score): the same operands, results and checks."""
+    require_device(X, U, V, b, mean_y, std_y, gt, bps, r2, out, pred, workspace)
+    K, T, N, C, r = _rrr_dims(X, gt, U, V, b, "rrr_wide_score")
+    for t, numel in ((mean_y, T * N), (std_y, T * N), (bps, N), (r2, N), (pred, K * T * N)):
+        if t is not None and (t.numel() != numel or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise L.VsError("rrr_wide_score: mean_y / std_y [T, N], bps / r2 [N], pred [K, T, N] dense float64")
+    if out.dtype != torch.float64 or out.numel() < 2:
+        raise L.VsError("rrr_wide_score: out must hold two float64")
+    need = rrr_wide_score_workspace_bytes(K, T, N)
+    if workspace is None:
+        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise L.VsError("rrr_wide_score: workspace too small")
+    check(lib().vs_rrr_wide_score(K, T, N, C, r, X.data_ptr(), U.data_ptr(), V.data_ptr(), b.data_ptr(),
+                                  mean_y.data_ptr(), std_y.data_ptr(), gt.data_ptr(), _f64_code(gt), ptr(pred),
+                                  bps.data_ptr(), r2.data_ptr(), out.data_ptr(), workspace.data_ptr(), stream()),
+          "vs_rrr_wide_score")
+    return out
+
+
+def gauss_weights(sigma):
+    """(weights float64 [2 radius + 1], radius) of scipy.ndimage.gaussian_filter1d(., sigma) with its default
+    truncate = 4, computed as scipy's _gaussian_kernel1d does."""
+    sigma = float(sigma)
+    if not sigma > 0:
+        raise L.VsError("gauss_smooth_time: sigma must be positive")
+    radius = int(4.0 * sigma + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    return phi / phi.sum(), radius
+
+
+def gauss_smooth_time(y, sigma, out=None):
+    """scipy.ndimage.gaussian_filter1d(y, sigma, axis=1) (mode 'reflect') for y [K, T, N] float32 / float64 on
+    the device, bit for bit (vs_gauss_smooth_time).  T >= radius + 1 with radius = int(4 sigma + 0.5)."""
+    require_device(y, out)
+    if y.dim() != 3 or y.dtype not in (torch.float32, torch.float64) or not y.is_contiguous():
+        raise L.VsError("gauss_smooth_time: y [K, T, N] dense float32 / float64")
+    w, radius = gauss_weights(sigma)
+    K, T, N = y.shape
+    if T < radius + 1:
+        raise L.VsError(f"gauss_smooth_time: T = {T} < radius + 1 = {radius + 1} (one reflection at each end)")
+    if out is None:
+        out = torch.empty_like(y)
+    elif out.shape != y.shape or out.dtype != y.dtype or not out.is_contiguous() or out.data_ptr() == y.data_ptr():
+        raise L.VsError("gauss_smooth_time: out is a dense tensor of y's shape and dtype, not y itself")
+    wd = torch.from_numpy(w).to(y.device)
+    check(lib().vs_gauss_smooth_time(K, T, N, y.data_ptr(), _f64_code(y), wd.data_ptr(), radius, out.data_ptr(),
+                                     stream()), "vs_gauss_smooth_time")
     return out
 
 

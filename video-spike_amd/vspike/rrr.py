@@ -13,6 +13,11 @@ tests; the closure, evaluated up to 20 times per fit, is the hot path and runs i
 (csrc/rrr.hip): one pass over y and X gives the loss and dU, dV, db with no autograd graph.  Scoring (clip,
 bits per spike, R^2 per trial) is `vs_rrr_score`.  Everything is float64 but y / gt, which stay in the dtype
 they come in (float32 in the reference's use).
+
+The RRR baseline `src/train_rrr.py` is the second half of this module: `RRRGD` (the reference's model with its
+sessions sharing V; inputs up to 1024 features run `vs_rrr_wide_loss_grad` / `vs_rrr_wide_score`, csrc/rrr_wide.hip),
+`prepare_rrr_inputs` (Gaussian smoothing, one-hot choice / block, standardisation, frame selection) and
+`train_rrr_baseline`.
 """
 from __future__ import annotations
 
@@ -226,3 +231,290 @@ def train_rrr(data_dict: dict, device=None, n_comp: int = 3, l2: float = 100.) -
         result[eid] = {"gt": y[1].cpu().numpy(), "pred": s["pred"].cpu().numpy(),
                        "bps": s["bps"].cpu().tolist(), "r2": s["r2"].cpu().tolist(), "eid": eid}
     return result
+
+
+# ---- the RRR baseline (src/train_rrr.py): sessions sharing V, wide inputs, feature preparation ------------------
+WIDE_MAX_FEATURES = 1024
+EMBEDDING_MODS = ("cebra", "pca", "ws", "whisker-video", "vit", "cm", "m", "c")       # train_rrr.py:119
+INPUT_MODS = ("me", "of", "of-2d", "of-2d-v", "all", "other", "me-all", "of-all") + EMBEDDING_MODS
+
+
+def check_dims_wide(C: int, r: int) -> None:
+    if not 1 <= C <= WIDE_MAX_FEATURES:
+        raise VsError(f"RRRGD: {C} features, supported 1..{WIDE_MAX_FEATURES} (the bias column not counted); "
+                      "raw pixel inputs ('whisker-video') are out of scope")
+    if not 1 <= r <= MAX_COMPONENTS:
+        raise VsError(f"RRRGD: {r} components, supported 1..{MAX_COMPONENTS}")
+
+
+def _is_wide(C: int) -> bool:
+    return C > MAX_FEATURES
+
+
+class RRRGD:
+    """The reference's RRRGD with its sessions (src/model/rrr.py:29-202): every session has its own U [N, C, r] and
+    b [N, 1, T]; one V [r, T] is shared by all.  `fit({eid: (X, y)})` takes standardised device tensors per
+    session, X [K, T, C+1] float64 with a last column of ones and y [K, T, N] float32 or float64; T is common,
+    K, N and C may differ.  Sessions with C <= 32 run vs_rrr_loss_grad, wider ones vs_rrr_wide_loss_grad."""
+
+    def __init__(self, n_comp: int = 3, l2: float = 100.):
+        self.n_comp, self.l2 = int(n_comp), float(l2)
+        self.eids, self._U, self._b, self._V = [], {}, {}, None
+        self.losses, self.n_iter, self.func_evals = [], 0, 0
+
+    def _check(self, X, y, what="RRRGD"):
+        if not (torch.is_tensor(X) and torch.is_tensor(y)) or X.dim() != 3 or y.dim() != 3 \
+                or X.shape[:2] != y.shape[:2]:
+            raise VsError(f"{what}: X [K, T, C+1] and y [K, T, N] device tensors per session")
+        check_dims_wide(X.shape[2] - 1, self.n_comp)
+        if X.dtype != torch.float64:
+            raise VsError(f"{what}: X must be float64 (the reference's bias column makes it so)")
+        if y.dtype not in (torch.float32, torch.float64):
+            raise VsError(f"{what}: y must be float32 or float64")
+
+    def fit(self, data: dict) -> "RRRGD":
+        """One default torch L-BFGS step over [U_0, b_0, U_1, b_1, ..., V] (the reference's ParameterDict order,
+        rrr.py:46-49,199).  The initial values are rrr.py:35-49 exactly: one RandomState(0), per session in dict
+        order a U and then a V draw, and the LAST session's V is the one kept.  Each b's master copy has its y's
+        dtype, for the reason in RRR.fit's docstring.  The closure adds the sessions' losses and dVs in session
+        order with plain float64 adds."""
+        if not isinstance(data, dict) or not data:
+            raise VsError("RRRGD.fit: {eid: (X, y)} with at least one session")
+        sess = {}
+        for eid, (X, y) in data.items():
+            self._check(X, y)
+            sess[eid] = (X.contiguous(), y.contiguous())
+        Ts = {X.shape[1] for X, _ in sess.values()}
+        if len(Ts) != 1:
+            raise VsError(f"RRRGD.fit: the sessions share V, so T must be equal across them (got {sorted(Ts)})")
+        T, r = Ts.pop(), self.n_comp
+        self.T, self.eids = T, list(sess)
+        dev = next(iter(sess.values()))[0].device
+        rs = np.random.RandomState(0)
+        U, b_master, b64, dU, db64, dVs, ws, fn = {}, {}, {}, {}, {}, {}, {}, {}
+        V0 = None
+        for eid, (X, y) in sess.items():
+            K, _, C1 = X.shape
+            N, C = y.shape[2], C1 - 1
+            U0 = rs.normal(size=(N, C, r)) / np.sqrt(T * r)                      # rrr.py:42
+            V0 = rs.normal(size=(r, T)) / np.sqrt(T * r)                         # rrr.py:43: the last one is kept
+            U[eid] = torch.from_numpy(U0).to(dev).requires_grad_(True)
+            b_master[eid] = _mean_trials(y).t().unsqueeze(1).contiguous().requires_grad_(True)    # rrr.py:44
+            b64[eid] = b_master[eid].detach().double()
+            dU[eid], db64[eid] = torch.zeros_like(U[eid]), torch.zeros_like(b64[eid])
+            dVs[eid] = torch.zeros(r, T, dtype=torch.float64, device=dev)
+            U[eid].grad, b_master[eid].grad = dU[eid], torch.zeros_like(b_master[eid])
+            wide = _is_wide(C)
+            fn[eid] = ops.rrr_wide_loss_grad if wide else ops.rrr_loss_grad
+            need = (ops.rrr_wide_loss_grad_workspace_bytes if wide else ops.rrr_loss_grad_workspace_bytes)(K, T, N, C)
+            ws[eid] = torch.empty(need // 8 + 2, dtype=torch.float64, device=dev)
+        V = torch.from_numpy(V0).to(dev).requires_grad_(True)
+        V.grad = torch.zeros_like(V)
+        losses = []
+
+        def closure():
+            with torch.no_grad():
+                total = None
+                for i, (eid, (X, y)) in enumerate(sess.items()):
+                    b64[eid].copy_(b_master[eid])
+                    loss = torch.empty(1, dtype=torch.float64, device=dev)
+                    fn[eid](X, y, U[eid], V, b64[eid], self.l2, loss, dU=dU[eid], dV=dVs[eid], db=db64[eid],
+                            workspace=ws[eid])
+                    b_master[eid].grad.copy_(db64[eid])
+                    if i == 0:
+                        total = loss
+                        V.grad.copy_(dVs[eid])
+                    else:
+                        total = total + loss
+                        V.grad.add_(dVs[eid])
+            losses.append(total)
+            return total[0]
+
+        params = [p for eid in sess for p in (U[eid], b_master[eid])] + [V]
+        opt = torch.optim.LBFGS(params)                                          # rrr.py:199
+        opt.step(closure)                                                        # rrr.py:177
+        st = opt.state[params[0]]
+        self.n_iter, self.func_evals = int(st["n_iter"]), int(st["func_evals"])
+        self.losses = torch.cat(losses).cpu().numpy()
+        with torch.no_grad():
+            for eid in sess:
+                b64[eid].copy_(b_master[eid])
+        self._U = {eid: U[eid].detach() for eid in sess}
+        self._b = b64
+        self._V = V.detach()
+        self._N = {eid: y.shape[2] for eid, (_, y) in sess.items()}
+        return self
+
+    def _known(self, eid):
+        if eid not in self._U:
+            raise VsError(f"RRRGD: no fitted session {eid!r} (sessions: {self.eids})")
+
+    def U(self, eid) -> torch.Tensor:
+        self._known(eid)
+        return self._U[eid]
+
+    def b(self, eid) -> torch.Tensor:
+        self._known(eid)
+        return self._b[eid]
+
+    @property
+    def V(self) -> torch.Tensor:
+        return self._V
+
+    def _check_session(self, eid, X, y, what):
+        self._known(eid)
+        self._check(X, y, what)
+        U = self._U[eid]
+        if X.shape[1] != self.T or X.shape[2] - 1 != U.shape[1] or y.shape[2] != U.shape[0]:
+            raise VsError(f"{what}: session {eid!r} was fitted with T {self.T}, C {U.shape[1]}, N {U.shape[0]}")
+
+    def mse(self, data: dict) -> torch.Tensor:
+        """sum (yhat - y)^2 over everything and every session given: the reference's `mse_val_mean`
+        (rrr.py:180-181), a device scalar; the sessions are added in dict order."""
+        total = None
+        for eid, (X, y) in data.items():
+            self._check_session(eid, X, y, "RRRGD.mse")
+            loss = torch.empty(1, dtype=torch.float64, device=X.device)
+            fn = ops.rrr_wide_loss_grad if _is_wide(X.shape[2] - 1) else ops.rrr_loss_grad
+            fn(X.contiguous(), y.contiguous(), self._U[eid], self._V, self._b[eid], 0.0, loss)
+            total = loss if total is None else total + loss
+        if total is None:
+            raise VsError("RRRGD.mse: {eid: (X, y)} with at least one session")
+        return total[0]
+
+    def score(self, eid, X: torch.Tensor, mean_y: torch.Tensor, std_y: torch.Tensor, gt: torch.Tensor,
+              want_pred: bool = True) -> dict:
+        """train_rrr.py:193-224 on a session's held-out trials: device tensors pred [K, T, N] (clipped rates),
+        bps [N], r2 [N], co_bps and r2_mean (scalars)."""
+        self._check_session(eid, X, gt, "RRRGD.score")
+        dev = X.device
+        K, T, N = gt.shape
+        pred = torch.empty(K, T, N, dtype=torch.float64, device=dev) if want_pred else None
+        bps, r2 = (torch.empty(N, dtype=torch.float64, device=dev) for _ in range(2))
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+        fn = ops.rrr_wide_score if _is_wide(X.shape[2] - 1) else ops.rrr_score
+        fn(X.contiguous(), self._U[eid], self._V, self._b[eid], mean_y.to(torch.float64).contiguous(),
+           std_y.to(torch.float64).contiguous(), gt.contiguous(), bps, r2, out, pred=pred)
+        return {"pred": pred, "bps": bps, "r2": r2, "co_bps": out[0], "r2_mean": out[1]}
+
+    def state_dict(self) -> dict:
+        """The layout of RRRGD.state_dict (rrr.py:64-71)."""
+        model = {}
+        for eid in self.eids:
+            model[f"{eid}_U"] = self._U[eid].cpu().clone()
+            model[f"{eid}_b"] = self._b[eid].cpu().clone()
+        model["V"] = self._V.cpu().clone()
+        return {"model": model, "l2": self.l2, "eids": list(self.eids), "N": sum(self._N.values()), "T": self.T,
+                "n_comp": self.n_comp}
+
+
+def _one_hot(col: torch.Tensor, frames: int):
+    """utils.py:114-119 for a (K, 1) column: (K, frames, number of distinct values) float64, the categories being
+    the sorted distinct values of this very column.  Returns (one-hot, categories)."""
+    uni = torch.unique(col)                                                      # sorted
+    ret = (col.reshape(-1, 1, 1) == uni.reshape(1, 1, -1)).to(torch.float64)
+    return ret.expand(-1, frames, -1), uni
+
+
+def prepare_rrr_inputs(data: dict, input_mod: str, idx=None, smooth_w=2, device=None):
+    """train_rrr.py:108-171 on the device: data[eid] = {'X': [train, val] (K, F, C), 'y': [train, val] (K, T, N)
+    counts, 'setup': {}}, numpy or torch, left as they are.  Per session (in sorted order): the raw validation
+    counts are kept as the ground truth; both y splits are smoothed along time (gaussian_filter1d, sigma
+    `smooth_w`); for the behaviour modes choice and block (the last two columns, constant within a trial) become
+    one-hot columns in front of the continuous ones; X and y are standardised with the train split's statistics;
+    the bias column is appended and the T frames `idx` of F are selected (default: the reference's draw
+    sort(choice(F - 1, T, replace=False)) from numpy's global generator, once for all sessions).
+    Returns (prepared, ground_truth): prepared[eid] = {'X': [..], 'y': [..], 'setup': {mean_X_Tv, std_X_Tv,
+    mean_y_TN, std_y_TN}} as device tensors, ground_truth[eid] the raw validation counts."""
+    if input_mod not in INPUT_MODS:
+        raise VsError(f"prepare_rrr_inputs: input_mod {input_mod!r} is none of {INPUT_MODS}")
+    if not isinstance(data, dict) or not data:
+        raise VsError("prepare_rrr_inputs: {eid: {'X': [train, val], 'y': [train, val]}} with at least one session")
+    eids = sorted(data)                                                          # train_rrr.py:112
+    loaded = {}
+    for eid in eids:
+        d = data[eid]
+        X = [_device_tensor(x, device or (x.device if torch.is_tensor(x) and x.is_cuda else "cuda")) for x in d["X"]]
+        y = [_device_tensor(v, X[0].device) for v in d["y"]]
+        if any(x.dim() != 3 for x in X) or any(v.dim() != 3 for v in y) or X[0].shape[1:] != X[1].shape[1:] \
+                or y[0].shape[1:] != y[1].shape[1:] or any(x.shape[0] != v.shape[0] for x, v in zip(X, y)):
+            raise VsError(f"prepare_rrr_inputs: session {eid!r}: X [K, F, C] and y [K, T, N] per split")
+        loaded[eid] = (X, y)
+    Ts = {y[0].shape[1] for _, y in loaded.values()}
+    if len(Ts) != 1:
+        raise VsError(f"prepare_rrr_inputs: T must be equal across sessions (got {sorted(Ts)})")
+    T = Ts.pop()
+    if idx is None:
+        F = loaded[eids[0]][0][0].shape[1]
+        if F - 1 < T:
+            raise VsError(f"prepare_rrr_inputs: cannot draw {T} of {F} - 1 frames")
+        idx = np.sort(np.random.choice(F - 1, T, replace=False))                 # train_rrr.py:48-49
+    idx = np.asarray(idx)
+    if idx.ndim != 1 or idx.dtype.kind not in "iu" or len(idx) != T:
+        raise VsError(f"prepare_rrr_inputs: idx must hold {T} frame indices (one per bin of y)")
+    prepared, ground_truth = {}, {}
+    for eid in eids:
+        X, y = loaded[eid]
+        dev = X[0].device
+        F = X[0].shape[1]
+        if idx.min() < 0 or idx.max() >= F:
+            raise VsError(f"prepare_rrr_inputs: idx must hold {T} frame indices below {F} (session {eid!r})")
+        ground_truth[eid] = y[1]                                                 # train_rrr.py:116
+        if input_mod in EMBEDDING_MODS:
+            if input_mod == "m":
+                X = [x[..., :3] for x in X]                                      # train_rrr.py:126
+        elif input_mod not in ("me", "of-2d"):                                   # train_rrr.py:129-141
+            const = 3 if input_mod in ("me-all", "of-all") else 2
+            cats, new = [], []
+            for x in X:
+                if x.shape[2] < const:
+                    raise VsError(f"prepare_rrr_inputs: {input_mod!r} needs at least {const} columns of X")
+                contin_dim = x.shape[2] - const
+                choice, c_cat = _one_hot(x[:, 0, -2:-1], F)
+                block, b_cat = _one_hot(x[:, 0, -1:], F)
+                new.append(torch.cat([choice, block, x[..., x.shape[2] - 2 - contin_dim:-2].double()], dim=2))
+                cats.append((c_cat, b_cat))
+            if not all(torch.equal(p, q) for p, q in zip(*cats)):
+                raise VsError(f"prepare_rrr_inputs: session {eid!r}: the two splits do not have the same choice / "
+                              "block categories, so their one-hot columns differ (the reference fails with a "
+                              "shape error at the standardisation)")
+            X = new
+        y = [ops.gauss_smooth_time(v.contiguous(), smooth_w) for v in y]         # train_rrr.py:118
+        mean_X, std_X = _std(X[0])                                               # train_rrr.py:144-145
+        mean_y, std_y = _std(y[0])
+        sel = torch.from_numpy(idx.astype(np.int64)).to(dev)
+        Xs, ys = [], []
+        for i in range(2):
+            x = _div(X[i] - mean_X, std_X).to(torch.float64)
+            ones = torch.ones(x.shape[0], x.shape[1], 1, dtype=torch.float64, device=dev)
+            Xs.append(torch.cat([x, ones], dim=2).index_select(1, sel).contiguous())   # train_rrr.py:156-163
+            ys.append(_div(y[i] - mean_y, std_y))
+        setup = dict(mean_X_Tv=mean_X, std_X_Tv=std_X, mean_y_TN=mean_y, std_y_TN=std_y)
+        if isinstance(data[eid].get("setup"), dict):
+            data[eid]["setup"].update(setup)
+        prepared[eid] = {"X": Xs, "y": ys, "setup": setup}
+    return prepared, ground_truth
+
+
+def train_rrr_baseline(data: dict, input_mod: str, idx=None, n_comp: int = 3, l2: float = 100., joint: bool = False,
+                       device=None):
+    """src/train_rrr.py's main() from the loaded dict on: prepare (prepare_rrr_inputs), fit and score.
+    joint = False is the script's loop, one RRRGD per session; joint = True fits all sessions in one RRRGD with a
+    shared V (train_model_main supports it; the script does not use it).
+    Returns ({eid: {'gt', 'pred', 'co_bps': [per neuron], 'r2': [per neuron], 'eid'}}, mean co-bps): the
+    reference's keys (train_rrr.py:230-236) and its 'mean bps' (the mean over sessions of each session's
+    NaN-ignoring mean over neurons)."""
+    prepared, ground_truth = prepare_rrr_inputs(data, input_mod, idx=idx, device=device)
+    models = {}
+    if joint:
+        m = RRRGD(n_comp=n_comp, l2=l2).fit({eid: (p["X"][0], p["y"][0]) for eid, p in prepared.items()})
+        models = {eid: m for eid in prepared}
+    result, test_bps = {}, []
+    for eid, p in prepared.items():
+        m = models.get(eid) or RRRGD(n_comp=n_comp, l2=l2).fit({eid: (p["X"][0], p["y"][0])})
+        gt = ground_truth[eid]
+        s = m.score(eid, p["X"][1], p["setup"]["mean_y_TN"], p["setup"]["std_y_TN"], gt)
+        test_bps.append(float(s["co_bps"]))
+        result[eid] = {"gt": gt.cpu().numpy(), "pred": s["pred"].cpu().numpy(), "co_bps": s["bps"].cpu().tolist(),
+                       "r2": s["r2"].cpu().tolist(), "eid": eid}
+    return result, float(np.mean(test_bps))
