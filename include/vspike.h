@@ -617,6 +617,37 @@ int vs_gauss_smooth_time(int64_t K, int64_t T, int64_t N, const void* y, int32_t
                          int64_t radius, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PCA of a video by block subspace iteration (csrc/pca.hip): the kernels under
+ * vspike.pca.PCA, which is get_pca_embedding (src/utils/utils.py:350-360) for the RRR baseline.
+ *   X [M, D] row-major, rows dense, VS_U8 or VS_F32 (`x_dtype`): M frames of D pixels, stored once;
+ *   mu [D] f64 the column means;  Xc = X - 1 mu^T is never written: an element is centred on its way into LDS,
+ *   x - mu_d in f64 rounded once to f32;  Q [D, L] f64 (rounded to f32 for the product), 1 <= L <= 32.
+ * Both products run on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32) with f32 accumulation over at most 128
+ * terms, then f64; partial sums of different workgroups are added in f64 in ascending order.  No atomics: equal
+ * inputs give bitwise equal outputs.  M >= 2, D >= 1, 1 <= L <= 32, else VS_EINVAL before any launch.  M, D, L
+ * need not be multiples of anything; X needs no alignment beyond its element's, f64 operands 8 bytes, the
+ * workspace 16 bytes.  Nothing outside the operands and the stated workspace is read or written.
+ * chunks(M) = the number of row chunks a reduction over M is split into: at most 16, one per 512 rows.
+ * ------------------------------------------------------------------------------------------ */
+/* mu[d] = (sum_m X[m,d]) / M in f64: rows ascending within a chunk, chunks ascending.
+   workspace: chunks(M) D doubles. */
+size_t vs_pca_colmean_workspace_bytes(int64_t M, int64_t D);
+int vs_pca_colmean(int64_t M, int64_t D, const void* X, int32_t x_dtype, double* mu, void* workspace, void* stream);
+/* Y [M, L] f64 = Xc Q.  workspace: roundup(D, 64) x 32 floats (Q in f32, zero padded). */
+size_t vs_pca_project_workspace_bytes(int64_t M, int64_t D, int64_t L);
+int vs_pca_project(int64_t M, int64_t D, int64_t L, const void* X, int32_t x_dtype, const double* mu,
+                   const double* Q, double* Y, void* workspace, void* stream);
+/* W [D, L] f64 = Xc^T (Xc Q): one step of the iteration, two passes over X (Y = Xc Q is kept in f32 in the
+   workspace).  workspace, each piece rounded up to 256 bytes: roundup(D, 64) x 32 floats (Q) +
+   roundup(M, 128) x 32 floats (Y) + chunks(M) D L doubles (partial W): 45 MB at M 60,000, D 18,260, L 15. */
+size_t vs_pca_gram_apply_workspace_bytes(int64_t M, int64_t D, int64_t L);
+int vs_pca_gram_apply(int64_t M, int64_t D, int64_t L, const void* X, int32_t x_dtype, const double* mu,
+                      const double* Q, double* W, void* workspace, void* stream);
+/* out[0..3] = rows per workgroup of the Y product, columns per workgroup of the W product, rows per reduction
+   chunk at the least, chunks at the most: what a test needs to place its shapes at the tiles' edges */
+int vs_pca_tiles(int32_t* out);
+
+/* ------------------------------------------------------------------------------------------
  * Trial shards (host side of the input path; replaces the per-trial webdataset tars of
  * src/prepare_data.py:210-235 read by src/loader/base.py:21-41).  Fixed-size records: raw uint8
  * frames (T, C, H, W) + f32 spike counts (ap_rows, ap_cols) + a 64-byte "<eid>_<trial>" key.
@@ -649,7 +680,7 @@ const char* vs_shard_last_error(void);
 #define VS_TIMER_LN_FWD   4   /* vs_layernorm_fwd */
 #define VS_TIMER_LN_BWD   5   /* vs_layernorm_bwd (+ its partial-sum reduction) */
 #define VS_TIMER_ADAMW    6   /* vs_adamw */
-#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd), vs_token_pool_*, vs_cls_embed_*, vs_embed_head_*, vs_info_nce, vs_rrr_*, vs_gauss_smooth_time */
+#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd), vs_token_pool_*, vs_cls_embed_*, vs_embed_head_*, vs_info_nce, vs_rrr_*, vs_gauss_smooth_time, vs_pca_* */
 /* per-product tags of the ViT block executor (vs_vit_layer_fwd / _bwd): its vs_gemm calls are
    charged to these instead of VS_TIMER_GEMM / VS_TIMER_GEMM_DW, so every product has its own timer */
 #define VS_TIMER_FWD_QKV   8   /* qkv = h1 Wqkv^T + b          (mv:233-236) */
@@ -729,6 +760,13 @@ int vs_ln_dispatch_counts(int64_t* out, int n);
 #define VS_RRR_PATH_SMOOTH 1   /* vs_gauss_smooth_time: one per call */
 #define VS_RRR_PATH_COUNT  2
 int vs_rrr_dispatch_counts(int64_t* out, int n);
+/* The PCA kernels' counters, one per call (vs_dispatch_reset zeroes them too): a group of their own because the
+   two groups above are pinned by tests. */
+#define VS_PCA_PATH_COLMEAN 0   /* vs_pca_colmean */
+#define VS_PCA_PATH_PROJECT 1   /* vs_pca_project */
+#define VS_PCA_PATH_GRAM    2   /* vs_pca_gram_apply */
+#define VS_PCA_PATH_COUNT   3
+int vs_pca_dispatch_counts(int64_t* out, int n);
 /* 1 when every compiled instance of the 256 x 256 forward / dX GEMM (VS_PATH_GEMM_G256) has no private
    (scratch) segment: its early-DMA wait counts the epilogue's stores exactly.  An instance that spills
    falls back to vmcnt(0) on its own; this is the test's view of the same check. */

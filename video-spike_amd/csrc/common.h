@@ -49,6 +49,8 @@ void count_path(int id);
 void count_ln(int kernel, bool bwd);
 // RRR baseline counters (VS_RRR_PATH_*, vs_rrr_dispatch_counts)
 void count_rrr(int id);
+// PCA counters (VS_PCA_PATH_*, vs_pca_dispatch_counts)
+void count_pca(int id);
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

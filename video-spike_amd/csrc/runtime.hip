@@ -57,6 +57,8 @@ static std::atomic<int64_t> g_dispatch[VS_PATH_COUNT];
 void count_path(int id) { g_dispatch[id].fetch_add(1, std::memory_order_relaxed); }
 static std::atomic<int64_t> g_rrr_dispatch[VS_RRR_PATH_COUNT];
 void count_rrr(int id) { g_rrr_dispatch[id].fetch_add(1, std::memory_order_relaxed); }
+static std::atomic<int64_t> g_pca_dispatch[VS_PCA_PATH_COUNT];
+void count_pca(int id) { g_pca_dispatch[id].fetch_add(1, std::memory_order_relaxed); }
 static std::atomic<int64_t> g_ln_dispatch[2 * VS_LN_KERNELS];
 void count_ln(int kernel, bool bwd) {
   g_ln_dispatch[(bwd ? VS_LN_KERNELS : 0) + kernel].fetch_add(1, std::memory_order_relaxed);
@@ -101,8 +103,9 @@ ScopedTimer::~ScopedTimer() {
 // 2: vs_vit_layer_grad.flags; 3: .chain; 4: bf16-mode a_pre holds gelu'(pre), d_h may be bf16,
 // knobs / dispatch counters / build id; 5: a_pre == NULL selects the fused MLP (vs_mlp_*);
 // 6: vs_vit_layer.fp8_ws / fp8_ws_bytes and dtype VS_FP8 (MX-FP8 forward products);
-// 7: vs_vit_layer.next_ln_* / ln1_ready (the next block's LayerNorm1 in the fused MLP epilogue)
-extern "C" int vs_version(void) { return 9; }
+// 7: vs_vit_layer.next_ln_* / ln1_ready (the next block's LayerNorm1 in the fused MLP epilogue);
+// 10: vs_pca_* (csrc/pca.hip) and vs_pca_dispatch_counts
+extern "C" int vs_version(void) { return 10; }
 extern "C" const char* vs_build_id(void) { return VS_BUILD_ID; }
 
 extern "C" int vs_knob_get(int k) {
@@ -134,11 +137,16 @@ extern "C" int vs_dispatch_reset(void) {
   for (auto& c : vs::g_dispatch) c.store(0, std::memory_order_relaxed);
   for (auto& c : vs::g_ln_dispatch) c.store(0, std::memory_order_relaxed);
   for (auto& c : vs::g_rrr_dispatch) c.store(0, std::memory_order_relaxed);
+  for (auto& c : vs::g_pca_dispatch) c.store(0, std::memory_order_relaxed);
   return VS_OK;
 }
 extern "C" int vs_rrr_dispatch_counts(int64_t* out, int n) {
   for (int i = 0; i < n && i < VS_RRR_PATH_COUNT; ++i) out[i] = vs::g_rrr_dispatch[i].load(std::memory_order_relaxed);
   return VS_RRR_PATH_COUNT;
+}
+extern "C" int vs_pca_dispatch_counts(int64_t* out, int n) {
+  for (int i = 0; i < n && i < VS_PCA_PATH_COUNT; ++i) out[i] = vs::g_pca_dispatch[i].load(std::memory_order_relaxed);
+  return VS_PCA_PATH_COUNT;
 }
 extern "C" int vs_ln_dispatch_counts(int64_t* out, int n) {
   for (int i = 0; i < n && i < 2 * VS_LN_KERNELS; ++i) out[i] = vs::g_ln_dispatch[i].load(std::memory_order_relaxed);

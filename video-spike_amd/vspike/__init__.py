@@ -9,6 +9,7 @@ from .config import DictConfig, config_from_kwargs, load_run_config, update_conf
 from .linear import Linear
 from .loss import InfoNCE, MSEMeanLoss, PoissonNLLMeanLoss, make_criterion, mse_mean, poisson_nll_mean
 from .optim import FusedAdamW
+from .pca import PCA, pca_embedding, pca_rrr_data
 from .r3d import R3D
 from .rrr import RRR, RRRGD, prepare_rrr_inputs, train_rrr, train_rrr_baseline
 from .temporal import VideoMAETemporal
@@ -25,6 +26,6 @@ NAME2MODEL = {
     "ContrastViT": ContrastViT,
 }
 
-__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "ContrastViT", "InfoNCE", "RRR", "train_rrr", "RRRGD", "prepare_rrr_inputs", "train_rrr_baseline", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
+__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "ContrastViT", "InfoNCE", "RRR", "train_rrr", "RRRGD", "prepare_rrr_inputs", "train_rrr_baseline", "PCA", "pca_embedding", "pca_rrr_data", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
            "mse_mean", "MSEMeanLoss", "make_criterion",
            "DictConfig", "update_config", "config_from_kwargs", "load_run_config"]

@@ -216,6 +216,14 @@ PROTOTYPES = {
                                          c_p, c_p, c_p, c_p, c_p, c_p]),
     "vs_gauss_smooth_time": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_i32, c_p, c_i64, c_p, c_p]),
     "vs_rrr_dispatch_counts": (ctypes.c_int, [ctypes.POINTER(c_i64), ctypes.c_int]),
+    "vs_pca_colmean_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "vs_pca_colmean": (ctypes.c_int, [c_i64, c_i64, c_p, c_i32, c_p, c_p, c_p]),
+    "vs_pca_project_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "vs_pca_project": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_i32, c_p, c_p, c_p, c_p, c_p]),
+    "vs_pca_gram_apply_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "vs_pca_gram_apply": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_i32, c_p, c_p, c_p, c_p, c_p]),
+    "vs_pca_tiles": (ctypes.c_int, [ctypes.POINTER(c_i32)]),
+    "vs_pca_dispatch_counts": (ctypes.c_int, [ctypes.POINTER(c_i64), ctypes.c_int]),
     "vs_timing_enable": (ctypes.c_int, [ctypes.c_int]),
     "vs_timing_collect": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double)]),
     "vs_timing_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
@@ -338,6 +346,20 @@ def rrr_dispatch_counts() -> dict:
     if total != n:
         raise VsError(f"RRR counters: the library has {total}, the binding names {n}")
     return {name: int(buf[i]) for i, name in enumerate(RRR_PATH_NAMES)}
+
+
+# vs_pca_dispatch_counts' ids (vspike.h VS_PCA_PATH_*): a third group, because tests pin the two above
+PCA_PATH_NAMES = ("pca_colmean", "pca_project", "pca_gram_apply")
+
+
+def pca_dispatch_counts() -> dict:
+    """Calls per PCA entry point since the last dispatch_reset()."""
+    n = len(PCA_PATH_NAMES)
+    buf = (c_i64 * n)()
+    total = lib().vs_pca_dispatch_counts(buf, n)
+    if total != n:
+        raise VsError(f"PCA counters: the library has {total}, the binding names {n}")
+    return {name: int(buf[i]) for i, name in enumerate(PCA_PATH_NAMES)}
 
 
 def total_path_count() -> int:

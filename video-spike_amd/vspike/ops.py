@@ -581,6 +581,94 @@ def gauss_smooth_time(y, sigma, out=None):
     return out
 
 
+# ---- PCA by subspace iteration (csrc/pca.hip): X [M, D] uint8 / float32 stored once, never centred in memory ----
+def pca_tiles() -> dict:
+    """The tile constants of csrc/pca.hip a test places its shapes by (vs_pca_tiles)."""
+    buf = (L.c_i32 * 4)()
+    check(lib().vs_pca_tiles(buf), "vs_pca_tiles")
+    return dict(zip(("rows", "cols", "chunk_rows", "max_chunks"), (int(v) for v in buf)))
+
+
+def _pca_x(X, what):
+    require_device(X)
+    if X.dim() != 2 or X.dtype not in (torch.uint8, torch.float32) or not X.is_contiguous():
+        raise L.VsError(f"{what}: X [M, D] dense uint8 / float32")
+    return X.shape[0], X.shape[1], (L.VS_U8 if X.dtype == torch.uint8 else L.VS_F32)
+
+
+def _pca_f64(t, shape, what, name):
+    require_device(t)
+    if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise L.VsError(f"{what}: {name} must be dense float64 of shape {tuple(shape)}")
+
+
+def _pca_ws(workspace, need, device, what):
+    if workspace is None:
+        return torch.empty(need // 8 + 2, dtype=torch.float64, device=device)
+    require_device(workspace)
+    if workspace.numel() * workspace.element_size() < need:
+        raise L.VsError(f"{what}: workspace too small")
+    return workspace
+
+
+def pca_colmean_workspace_bytes(M, D):
+    return int(lib().vs_pca_colmean_workspace_bytes(M, D))
+
+
+def pca_colmean(X, mu=None, workspace=None):
+    """mu [D] float64 = the column means of X [M, D] (vs_pca_colmean), summed in an order fixed by (M, D)."""
+    M, D, code = _pca_x(X, "pca_colmean")
+    if mu is None:
+        mu = torch.empty(D, dtype=torch.float64, device=X.device)
+    _pca_f64(mu, (D,), "pca_colmean", "mu")
+    ws = _pca_ws(workspace, pca_colmean_workspace_bytes(M, D), X.device, "pca_colmean")
+    check(lib().vs_pca_colmean(M, D, X.data_ptr(), code, mu.data_ptr(), ws.data_ptr(), stream()), "vs_pca_colmean")
+    return mu
+
+
+def pca_project_workspace_bytes(M, D, Lq):
+    return int(lib().vs_pca_project_workspace_bytes(M, D, Lq))
+
+
+def pca_project(X, mu, Q, Y=None, workspace=None):
+    """Y [M, L] float64 = (X - 1 mu^T) Q for Q [D, L] float64, 1 <= L <= 32 (vs_pca_project)."""
+    M, D, code = _pca_x(X, "pca_project")
+    _pca_f64(mu, (D,), "pca_project", "mu")
+    if Q.dim() != 2:
+        raise L.VsError("pca_project: Q [D, L]")
+    Lq = Q.shape[1]
+    _pca_f64(Q, (D, Lq), "pca_project", "Q")
+    if Y is None:
+        Y = torch.empty(M, Lq, dtype=torch.float64, device=X.device)
+    _pca_f64(Y, (M, Lq), "pca_project", "Y")
+    ws = _pca_ws(workspace, pca_project_workspace_bytes(M, D, Lq), X.device, "pca_project")
+    check(lib().vs_pca_project(M, D, Lq, X.data_ptr(), code, mu.data_ptr(), Q.data_ptr(), Y.data_ptr(), ws.data_ptr(),
+                               stream()), "vs_pca_project")
+    return Y
+
+
+def pca_gram_apply_workspace_bytes(M, D, Lq):
+    return int(lib().vs_pca_gram_apply_workspace_bytes(M, D, Lq))
+
+
+def pca_gram_apply(X, mu, Q, W=None, workspace=None):
+    """W [D, L] float64 = Xc^T (Xc Q) with Xc = X - 1 mu^T: one step of the subspace iteration
+    (vs_pca_gram_apply)."""
+    M, D, code = _pca_x(X, "pca_gram_apply")
+    _pca_f64(mu, (D,), "pca_gram_apply", "mu")
+    if Q.dim() != 2:
+        raise L.VsError("pca_gram_apply: Q [D, L]")
+    Lq = Q.shape[1]
+    _pca_f64(Q, (D, Lq), "pca_gram_apply", "Q")
+    if W is None:
+        W = torch.empty(D, Lq, dtype=torch.float64, device=X.device)
+    _pca_f64(W, (D, Lq), "pca_gram_apply", "W")
+    ws = _pca_ws(workspace, pca_gram_apply_workspace_bytes(M, D, Lq), X.device, "pca_gram_apply")
+    check(lib().vs_pca_gram_apply(M, D, Lq, X.data_ptr(), code, mu.data_ptr(), Q.data_ptr(), W.data_ptr(),
+                                  ws.data_ptr(), stream()), "vs_pca_gram_apply")
+    return W
+
+
 def poisson_nll(log_rate, target, loss_out, dx=None, grad_scale=1.0, workspace=None):
     require_device(log_rate, target, loss_out)
     n = log_rate.numel()
