@@ -648,6 +648,33 @@ int vs_pca_gram_apply(int64_t M, int64_t D, int64_t L, const void* X, int32_t x_
 int vs_pca_tiles(int32_t* out);
 
 /* ------------------------------------------------------------------------------------------
+ * The contrastive loader's frame transform (csrc/contrast_loader.hip): what the reference
+ * does per frame in ContrastDataset.__getitem__ (src/loader/contrast.py:65-93) with the transforms of
+ * src/pretrain.py:60-66, as one launch:
+ *   out[g, 0] = (Resize(video[idx[g], 0] / 255) - mean) / std,   g = 0 .. G-1
+ *   video (F, 1, H, W) dense, VS_U8 or VS_F32 (`in_dtype`), on the device;  idx [G] int64 on the device;
+ *   out (G, 1, S, S) f32 dense.
+ * Resize is torch's bilinear interpolate with align_corners=False, antialias=True (torchvision's Resize on a float
+ * tensor), width first, then height; its weights and sums are f64 here, each sum rounded once to f32; the pixel
+ * scaling and the normalisation are f32 with IEEE results.  H == W == S gives (f32(pixel) / 255 - mean) / std bit
+ * for bit.  1 <= S <= 512, 1 <= H, W <= 8 S (at most 17 taps per axis), F >= 1, 0 <= G <= 65535, std != 0, else
+ * VS_EINVAL before any launch.  An idx value outside [0, F) reads nothing and fills its output frame with NaN
+ * (vspike.ops.contrast_frames checks the indices on the host first).  `out` 16-byte aligned and S % 4 == 0 take
+ * the 16-byte stores.  No atomics; nothing outside `out` and the workspace is written.
+ * workspace: vs_contrast_frames_workspace_bytes(H, W, S) bytes, 8-byte aligned: the two axes' f64 weight tables,
+ * a function of (H, W, S) alone.  weights_ready = 0 fills them first (one small launch); a caller that kept the
+ * workspace of an earlier call with the same (H, W, S), ordered before this one, passes 1 and saves that launch.
+ * The tables hold weights only: whatever they contain, no address depends on them.
+ * ------------------------------------------------------------------------------------------ */
+size_t vs_contrast_frames_workspace_bytes(int64_t H, int64_t W, int64_t S);   /* 0 outside the supported extents */
+int vs_contrast_frames(int32_t in_dtype, int64_t F, int64_t H, int64_t W, const void* video, const int64_t* idx,
+                       int64_t G, int64_t S, float mean, float std, float* out, void* workspace,
+                       int32_t weights_ready, void* stream);
+/* out[0..5] = how (H, W, S) is split: output rows per workgroup, workgroups per frame, source rows staged per
+   workgroup, width taps, height taps, LDS bytes: what a test needs to place its shapes */
+int vs_contrast_frames_plan(int64_t H, int64_t W, int64_t S, int32_t* out);
+
+/* ------------------------------------------------------------------------------------------
  * Trial shards (host side of the input path; replaces the per-trial webdataset tars of
  * src/prepare_data.py:210-235 read by src/loader/base.py:21-41).  Fixed-size records: raw uint8
  * frames (T, C, H, W) + f32 spike counts (ap_rows, ap_cols) + a 64-byte "<eid>_<trial>" key.
@@ -680,7 +707,7 @@ const char* vs_shard_last_error(void);
 #define VS_TIMER_LN_FWD   4   /* vs_layernorm_fwd */
 #define VS_TIMER_LN_BWD   5   /* vs_layernorm_bwd (+ its partial-sum reduction) */
 #define VS_TIMER_ADAMW    6   /* vs_adamw */
-#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd), vs_token_pool_*, vs_cls_embed_*, vs_embed_head_*, vs_info_nce, vs_rrr_*, vs_gauss_smooth_time, vs_pca_* */
+#define VS_TIMER_MISC     7   /* vs_cast, vs_colsum, vs_patch_im2col, vs_poisson_nll(_bwd), vs_token_pool_*, vs_cls_embed_*, vs_embed_head_*, vs_info_nce, vs_rrr_*, vs_gauss_smooth_time, vs_pca_*, vs_contrast_frames */
 /* per-product tags of the ViT block executor (vs_vit_layer_fwd / _bwd): its vs_gemm calls are
    charged to these instead of VS_TIMER_GEMM / VS_TIMER_GEMM_DW, so every product has its own timer */
 #define VS_TIMER_FWD_QKV   8   /* qkv = h1 Wqkv^T + b          (mv:233-236) */

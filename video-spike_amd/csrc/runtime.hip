@@ -105,7 +105,8 @@ ScopedTimer::~ScopedTimer() {
 // 6: vs_vit_layer.fp8_ws / fp8_ws_bytes and dtype VS_FP8 (MX-FP8 forward products);
 // 7: vs_vit_layer.next_ln_* / ln1_ready (the next block's LayerNorm1 in the fused MLP epilogue);
 // 10: vs_pca_* (csrc/pca.hip) and vs_pca_dispatch_counts
-extern "C" int vs_version(void) { return 10; }
+// 11: vs_contrast_frames (csrc/contrast_loader.hip)
+extern "C" int vs_version(void) { return 11; }
 extern "C" const char* vs_build_id(void) { return VS_BUILD_ID; }
 
 extern "C" int vs_knob_get(int k) {

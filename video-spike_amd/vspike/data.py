@@ -15,6 +15,10 @@ MI355X-first changes:
     a copy stream, and the consumer's stream waits on an event, so loading overlaps the train step.
 Batch order: a seeded per-epoch permutation (the reference's webdataset shard shuffle + 10000-sample
 buffer, src/loader/base.py:21-23, is not reproduced; sample order is not part of parity).
+
+The contrastive pretraining input (src/loader/contrast.py, src/loader/make.py:33-60) is `ContrastFrames` /
+`make_contrast_loader` below: a session's video held on the device as uint8, a batch of (ref, pos, neg) frames made
+by one vs_contrast_frames launch, and there the sample order IS the reference's, draw for draw.
 """
 from __future__ import annotations
 
@@ -248,3 +252,195 @@ class ShardLoader:
             stop.set()
             free.put(0)
             th.join(timeout=10)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The contrastive pretraining loader
+# ----------------------------------------------------------------------------------------------------------------
+class ContrastBatch(dict):
+    """{'ref', 'pos', 'neg'}: three (b, 1, S, S) views of one (3b, 1, S, S) buffer, kept as `.all`."""
+    all: torch.Tensor = None
+
+
+def _device_frames(data, device, transform):
+    """(F, 1, H, W) frames on the device in their own dtype: uint8 stays uint8; anything else becomes float32 (the
+    reference's `torch.tensor(video, dtype=float32)`), or uint8 without a transform (its `dtype=torch.uint8`)."""
+    v = torch.as_tensor(data)
+    if v.dim() != 5 or v.shape[2] != 1:
+        raise ValueError("ContrastFrames: video splits must be (n, t, 1, H, W)")
+    if v.dtype != torch.uint8:
+        v = v.to(torch.float32 if transform else torch.uint8)
+    return v.reshape((-1,) + tuple(v.shape[2:])).contiguous().to(device)
+
+
+class ContrastFrames:
+    """The reference's `ContrastDataset` under its `DataLoader` (src/loader/contrast.py, src/loader/make.py:33-60)
+    as one iterable over a session's video that stays on the device, from the dict `load_h5_file` returns for the
+    session: `train_X / val_X / test_X` (n, t, 1, H, W), `*_y`, `*_timestamp`.
+
+    mode 'pretrain': the frames of the three splits (train, val, test) are stored once in their own dtype; the
+    reference's timestamp sort is kept as an index map, the video is not permuted.  A batch is {'ref', 'pos', 'neg'},
+    three (b, 1, S, S) float32 views of one buffer that ONE vs_contrast_frames launch over 3b indices fills
+    (`fused(batch)` is that buffer, for ContrastTrainer.step_fused).  The host's work per batch is the index draw
+    and one small upload; no frame crosses the host link after construction.
+
+    Sampling is the reference's, draw for draw.  The batch order comes from torch's RandomSampler / BatchSampler
+    (shuffle, no drop_last) seeded from torch's global generator exactly as a DataLoader seeds them (one draw for
+    the iterator's base seed, one for the permutation).  For each item i of a batch, in order,
+        pos = int(np.random.uniform(max(0, i - idx_offset), min(F, i + idx_offset + 1)))
+        neg = int(np.random.uniform(0, F)), drawn again while it equals i
+    from numpy's global generator, when the batch is made (not per epoch), so that generator stands where the
+    reference's stands at every batch boundary (ContrastTrainer.validate draws from it between passes).
+    With `time_offset` the positive is np.random.choice over the frames with |timestamp - timestamp[i]| <=
+    time_offset.  A quirk of the reference is kept: its __init__ overwrites the timestamps with
+    linspace(0, len - 1, len) "if timestamp is None", but in pretrain mode that name has just been rebound to the
+    concatenated timestamps, so the real (sorted) timestamps are used there although make_contrast_loader never
+    passes the argument; only the trial modes get the linspace, where nothing reads it.  The fixture pins this.
+    Fewer than 2 frames is an error (the reference's negative draw would never end).
+
+    mode 'train' / 'val' / 'test': item i is trial i, {'ref': (1, t, 1, S, S), 'neural': (1, T, N)} (batch_size 1,
+    the form ContrastTrainer.validate takes), one launch per batch over the trials' frames, in order unless
+    `shuffle`.
+
+    transform=None: frames come back uint8 and untouched, as the reference's do (plain indexing, no kernel).
+
+    Data parallel (`rank`, `world`, ShardLoader's convention): every rank walks the same permutation (seed torch's
+    global generator alike on every rank) in global batches of batch_size * world, rank r takes slice r, and an
+    incomplete last global batch is filled from the start of the permutation; each rank draws positives and
+    negatives for its own items only, from its own numpy generator, as the reference's separate processes do.
+    This is this project's rule: what `accelerate` does to the reference's DataLoader is not reproduced.
+
+    frame_fn(video, idx, size, mean, std) -> frames replaces the kernel call (the CPU tests' seam)."""
+
+    MODES = ("pretrain", "train", "val", "test")
+
+    def __init__(self, data, mode="pretrain", batch_size=512, shuffle=True, size=144, idx_offset=4, time_offset=None,
+                 transform=True, mean=0.5, std=0.5, device="cuda", rank=0, world=1, frame_fn=None):
+        if mode not in self.MODES:
+            raise ValueError(f"ContrastFrames: invalid mode {mode!r}")
+        self.mode, self.batch_size, self.shuffle = mode, int(batch_size), bool(shuffle)
+        self.size, self.idx_offset, self.time_offset = int(size), idx_offset, time_offset
+        self.transform, self.mean, self.std = bool(transform), float(mean), float(std)
+        self.device, self.rank, self.world = torch.device(device), int(rank), int(world)
+        if self.batch_size < 1:
+            raise ValueError("ContrastFrames: batch_size must be positive")
+        if not (0 <= self.rank < self.world):
+            raise ValueError(f"ContrastFrames: rank {rank} outside world {world}")
+        self._frame_fn = frame_fn
+        splits = ("train", "val", "test") if mode == "pretrain" else (mode,)
+        videos = [np.asarray(data[f"{s}_X"]) for s in splits]
+        if len({v.shape[1:] for v in videos}) != 1:
+            raise ValueError("ContrastFrames: the splits differ in (t, 1, H, W)")
+        self.video = _device_frames(np.concatenate(videos, axis=0) if len(videos) > 1 else videos[0], self.device,
+                                    self.transform)
+        self.frames_per_trial = int(videos[0].shape[1])
+        self.num_frames = int(self.video.shape[0])
+        if mode == "pretrain":
+            stamps = np.concatenate([np.asarray(data[f"{s}_timestamp"]) for s in splits], axis=0).reshape(-1)
+            if stamps.shape[0] != self.num_frames:
+                raise ValueError("ContrastFrames: one timestamp per frame expected")
+            if self.num_frames < 2:
+                raise ValueError("ContrastFrames: pretraining needs at least 2 frames (no negative exists otherwise)")
+            self.sort = np.argsort(stamps)                    # item i is stored frame sort[i]
+            self.timestamp = stamps[self.sort]
+            self.num_items = self.num_frames
+        else:
+            self.labels = torch.as_tensor(np.asarray(data[f"{mode}_y"]))
+            self.num_items = int(videos[0].shape[0])
+            self.timestamp = np.linspace(0, self.num_items - 1, self.num_items)
+            self._arange = torch.arange(self.num_frames, dtype=torch.int64, device=self.device)
+
+    def __len__(self):
+        g = self.batch_size * self.world
+        return -(-self.num_items // g)
+
+    # ---- sampling (host) ----
+    def _batches(self):
+        """This rank's batches of item numbers for one pass, drawing from torch's global generator as a DataLoader
+        over the dataset does."""
+        from torch.utils.data import BatchSampler, RandomSampler, SequentialSampler
+        items = range(self.num_items)
+        sampler = RandomSampler(items) if self.shuffle else SequentialSampler(items)
+        torch.empty((), dtype=torch.int64).random_()          # the DataLoader iterator's base seed
+        if self.world == 1:
+            yield from BatchSampler(sampler, self.batch_size, drop_last=False)
+            return
+        order = list(sampler)
+        bs, g = self.batch_size, self.batch_size * self.world
+        n_glob = -(-len(order) // g)
+        order = (order * (1 + (n_glob * g) // len(order)))[:n_glob * g]     # fill from the start
+        for k in range(n_glob):
+            yield order[k * g + self.rank * bs: k * g + (self.rank + 1) * bs]
+
+    def _select_pos(self, i: int) -> int:
+        if self.time_offset is None:
+            lo, hi = max(0, i - self.idx_offset), min(self.num_frames, i + self.idx_offset + 1)
+            return int(np.random.uniform(lo, hi))
+        valid = np.where(abs(self.timestamp - self.timestamp[i]) <= self.time_offset)[0]
+        return int(np.random.choice(valid)) if valid.size > 0 else i
+
+    def _select_neg(self, i: int) -> int:
+        while True:
+            j = int(np.random.uniform(0, self.num_frames))
+            if j != i:
+                return j
+
+    def draw(self, items) -> np.ndarray:
+        """(b, 3) item numbers ref, pos, neg for a batch of items, drawn in the reference's order."""
+        out = np.empty((len(items), 3), dtype=np.int64)
+        for k, i in enumerate(items):
+            out[k] = (i, self._select_pos(i), self._select_neg(i))
+        return out
+
+    # ---- frames (device) ----
+    def _frames(self, idx: torch.Tensor) -> torch.Tensor:
+        if not self.transform:
+            return self.video[idx]
+        if self._frame_fn is not None:
+            return self._frame_fn(self.video, idx, self.size, self.mean, self.std)
+        from . import ops
+        return ops.contrast_frames(self.video, idx, self.size, self.mean, self.std, check_idx=False)
+
+    def _upload(self, idx: np.ndarray) -> torch.Tensor:
+        if idx.size and (idx.min() < 0 or idx.max() >= self.num_frames):
+            raise IndexError("ContrastFrames: frame index out of range")
+        t = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64))
+        if self.device.type != "cuda":
+            return t
+        return t.pin_memory().to(self.device, non_blocking=True)
+
+    def fused(self, batch) -> torch.Tensor:
+        """The (3b, 1, S, S) buffer [ref | pos | neg] behind a pretrain batch."""
+        x = getattr(batch, "all", None)
+        if x is None:
+            raise ValueError("ContrastFrames.fused: not a batch of this loader's pretrain mode")
+        return x
+
+    def __iter__(self):
+        t = self.frames_per_trial
+        for items in self._batches():
+            items = [int(i) for i in items]
+            if self.mode == "pretrain":
+                tri = self.draw(items)
+                x = self._frames(self._upload(self.sort[tri.T.reshape(-1)]))       # [ref | pos | neg]
+                b = len(items)
+                out = ContrastBatch(ref=x[:b], pos=x[b:2 * b], neg=x[2 * b:])
+                out.all = x
+                yield out
+            else:
+                if items == list(range(items[0], items[0] + len(items))):          # a run of trials: no upload
+                    idx = self._arange[items[0] * t:(items[-1] + 1) * t]
+                else:
+                    idx = self._upload((np.asarray(items)[:, None] * t + np.arange(t)[None]).reshape(-1))
+                x = self._frames(idx)
+                yield {"ref": x.view((len(items), t) + tuple(x.shape[1:])),
+                       "neural": self.labels[items].to(self.device, non_blocking=True)}
+
+
+def make_contrast_loader(data, mode="pretrain", batch_size=512, shuffle=True, size=144, idx_offset=4, time_offset=None,
+                         transform=True, device="cuda", rank=0, world=1, **kw):
+    """The reference's make_contrast_loader (src/loader/make.py:33-60) on the loaded session dict `data` (where it
+    takes the .h5 path and the session id): (loader, 1), as it returns.  transform: True = Resize((size, size)) +
+    Normalize([0.5], [0.5]), the reference's (src/pretrain.py:60-66), on the device; None = raw uint8 frames."""
+    return ContrastFrames(data, mode=mode, batch_size=batch_size, shuffle=shuffle, size=size, idx_offset=idx_offset,
+                          time_offset=time_offset, transform=transform, device=device, rank=rank, world=world, **kw), 1

@@ -764,3 +764,60 @@ def video_preprocess(video, frame_idx, size=224, mean=(0.485, 0.456, 0.406), std
     check(lib().vs_video_preprocess(code, B, T, H, W, video.data_ptr(), fi, len(idx), size, m, sd, out.data_ptr(),
                                     stream()), "vs_video_preprocess")
     return out
+
+
+# ---- the contrastive loader's frame transform (csrc/contrast_loader.hip) ----
+def contrast_frames_plan(H, W, size) -> dict:
+    """How vs_contrast_frames splits (H, W) -> size: what a test places its shapes by (vs_contrast_frames_plan)."""
+    buf = (L.c_i32 * 6)()
+    check(lib().vs_contrast_frames_plan(int(H), int(W), int(size), buf), "vs_contrast_frames_plan")
+    return dict(zip(("rows", "bands", "src_rows", "taps_w", "taps_h", "lds_bytes"), (int(v) for v in buf)))
+
+
+_CONTRAST_TABLES = {}     # (device, stream, H, W, S) -> the f64 weight tables vs_contrast_frames filled on that stream
+
+
+def contrast_frames(video, idx, size=144, mean=0.5, std=0.5, out=None, check_idx=True):
+    """out (G, 1, size, size) f32 = Normalize(mean, std)(Resize((size, size))(video[idx] / 255)): the reference's
+    per-frame transform (src/loader/contrast.py:65-93 with src/pretrain.py:60-66) in one launch (vs_contrast_frames).
+    video (F, 1, H, W) uint8 or float32 on the device, idx G int64 source-frame numbers on the device.
+    check_idx: the indices are checked against [0, F) on the host before the launch, which waits for `idx`; a
+    caller that drew them on the host (vspike.data.ContrastFrames) checks there and passes False.  Unchecked, an
+    index out of range reads nothing and gives a frame of NaN.
+    The weight tables of a geometry (a few KB) are filled by the first call on a stream and kept for the later ones."""
+    require_device(video, idx, out)
+    if video.dim() != 4 or video.shape[1] != 1:
+        raise L.VsError("contrast_frames: video (F, 1, H, W)")
+    if video.dtype == torch.uint8:
+        code = L.VS_U8
+    elif video.dtype == torch.float32:
+        code = L.VS_F32
+    else:
+        raise L.VsError("contrast_frames: float32 or uint8 frames")
+    if not video.is_contiguous():
+        raise L.VsError("contrast_frames: video must be dense (it is stored once; no copy is made here)")
+    if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != video.device:
+        raise L.VsError("contrast_frames: idx must be a dense 1-D int64 tensor on the video's device")
+    F, _, H, W = video.shape
+    G, S = idx.numel(), int(size)
+    need = int(lib().vs_contrast_frames_workspace_bytes(H, W, S))
+    if need == 0:
+        raise L.VsError("contrast_frames: 1 <= size <= 512 and 1 <= H, W <= 8 size")
+    if check_idx and G and (int(idx.min()) < 0 or int(idx.max()) >= F):
+        raise L.VsError(f"contrast_frames: frame index outside [0, {F})")
+    if out is None:
+        out = torch.empty(G, 1, S, S, dtype=torch.float32, device=video.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (G, 1, S, S) or not out.is_contiguous() or \
+            out.device != video.device:
+        raise L.VsError(f"contrast_frames: out must be a dense float32 ({G}, 1, {S}, {S}) tensor on the video's device")
+    st = stream()
+    key = (video.device.index, st.value, H, W, S)
+    table = _CONTRAST_TABLES.get(key)
+    ready = table is not None
+    if not ready:
+        table = torch.empty(need // 8, dtype=torch.float64, device=video.device)
+    check(lib().vs_contrast_frames(code, F, H, W, video.data_ptr(), idx.data_ptr(), G, S, float(mean), float(std),
+                                   out.data_ptr(), table.data_ptr(), int(ready), st), "vs_contrast_frames")
+    if G:
+        _CONTRAST_TABLES[key] = table
+    return out

@@ -77,6 +77,19 @@ class ContrastTrainer:
         res["loss"].backward()
         return self._finish(res)
 
+    def step_fused(self, frames, n: int) -> dict:
+        """`step` on the views already side by side: frames (2n + m, C, H, W) = [ref | pos | neg], as
+        vspike.data.ContrastFrames.fused(batch) hands them over (one buffer, filled by one launch), so the
+        `torch.cat` of `step` and its copy of every frame are skipped.  Same forward, loss and update as
+        step(frames[:n], frames[n:2n], frames[2n:])."""
+        if frames.dim() != 4 or not 0 < 2 * n < frames.shape[0]:
+            raise ValueError("ContrastTrainer.step_fused: frames (2n + m, C, H, W) with m >= 1")
+        out = self.model(frames)
+        z, temp = out["z"], out["temp"]
+        res = self.criterion({"z": z[:n], "temp": temp}, {"z": z[n:2 * n], "temp": temp}, {"z": z[2 * n:], "temp": temp})
+        res["loss"].backward()
+        return self._finish(res)
+
     def step_three_calls(self, ref, pos, neg) -> dict:
         """The reference trainer's literal form: three forwards alive before one backward.  Refused while a
         data-parallel gradient sink is attached (the sink reduces one backward per step)."""
@@ -125,6 +138,48 @@ class ContrastTrainer:
         data = {eid: {"X": [x[:, sel, :] for x in X], "y": y, "setup": {}}}
         res = train_rrr(data)
         return {"val_bps": float(np.nanmean(res[eid]["bps"]))}
+
+
+    def fit(self, loader, train_loader, val_loader, max_steps: int = 1000, path: Optional[str] = None,
+            eid: str = "session") -> dict:
+        """`src/trainer/contrast.py:35-59`: passes over the pretrain `loader` until `max_steps` steps are taken,
+        `validate(train_loader, val_loader)` after every pass, the one `max_steps` cuts short included; the best
+        val_bps is kept and, with `path`, the model's `reference_state_dict()` is saved there on every improvement
+        (the reference's best_model.pth; a NaN val_bps never improves, as there).  A loader with `fused` (vspike.data.
+        ContrastFrames) feeds step_fused, any other iterable of {'ref', 'pos', 'neg'} feeds step.
+        Returns {'steps': the per-step loss dicts (device tensors: nothing is read back per step), 'val_bps': one per
+        pass, 'best_val_bps', 'best_pass'}.  No wandb, no progress bar."""
+        steps, vals, best, best_pass = [], [], -float("inf"), None
+        fused = getattr(loader, "fused", None)
+        self.model.train()
+        while len(steps) < max_steps:
+            before = len(steps)
+            for batch in loader:
+                if fused is not None:
+                    steps.append(self.step_fused(fused(batch), batch["ref"].shape[0]))
+                else:
+                    steps.append(self.step(batch["ref"], batch["pos"], batch["neg"]))
+                if len(steps) >= max_steps:
+                    break
+            if len(steps) == before:
+                raise ValueError("ContrastTrainer.fit: the pretrain loader gave no batch")
+            val = self.validate(train_loader, val_loader, eid=eid)["val_bps"]
+            vals.append(val)
+            if val > best:
+                best, best_pass = val, len(vals) - 1
+                if path is not None:
+                    torch.save(self.model.reference_state_dict(), path)
+        return {"steps": steps, "val_bps": vals, "best_val_bps": best, "best_pass": best_pass}
+
+    @torch.no_grad()
+    def load_best(self, path: str) -> bool:
+        """The reference's `transform(use_best=True)` (contrast.py:170-173, 70-78): load the weights `fit` saved at
+        `path`; False, and the model as it is, when there is no such file."""
+        import os
+        if not os.path.exists(path):
+            return False
+        self.model.load_reference_state_dict(torch.load(path, map_location="cpu"))
+        return True
 
 
 class Trainer:
