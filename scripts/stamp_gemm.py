@@ -1,4 +1,5 @@
-"""Phase timeline of the whole-K GEMM (qkv shape; N=768 EPI=gelu: fc1) from a -DVS_STAMP build.
+"""Phase timeline of the whole-K GEMM (qkv shape; N=768 EPI=gelu: fc1) from a -DVS_STAMP build
+(python scripts/variant_build.py stamp VS_STAMP gemm_wholek.hip).
 usage: VSPIKE_LIB=.../libvspike_stamp.so [N=768 EPI=gelu] python scripts/stamp_gemm.py"""
 import ctypes
 import os

@@ -1,4 +1,5 @@
-"""Phase timeline of the row-panel GEMM from a -DVS_STAMP build (shape via env M N K, BKC=0/1).
+"""Phase timeline of the row-panel GEMM from a -DVS_STAMP build (shape via env M N K, BKC=0/1;
+python scripts/variant_build.py stamp VS_STAMP gemm_wholek.hip).
 usage: VSPIKE_LIB=.../libvspike_stamp.so python scripts/stamp_panel.py"""
 import ctypes
 import os

@@ -32,7 +32,7 @@
 namespace vs {
 
 // [64 k][64 rows] bf16 LDS image of an M/N-contiguous operand: the 8-KiB image of OperandBf16<64,
-// KC=false> in gemm.hip (16-B chunk XOR on k, read back transposed by ds_read_tr16_b64).
+// KC=false> in gemm_tiles.h (16-B chunk XOR on k, read back transposed by ds_read_tr16_b64).
 __device__ __forceinline__ int dw_swz(int k) { return 2 * (((k >> 1) & 1) | (((k >> 3) & 1) << 1)); }
 
 // LDS-DMA of one 8-KiB image: 8 pieces of 8 k-rows x 128 B; with NW waves, wave `wid` issues
@@ -512,7 +512,7 @@ __global__ __launch_bounds__(256) void gemm_dw_reduce_few(const float* __restric
 //         for A and B: it changes only the f32 summation order).
 // Wave w of a workgroup takes steps w, w+4, ... of the workgroup's K slice with U steps of loads in
 // flight; the four wave tiles are added through LDS in wave order and the workgroup's f32 partial
-// [M][N] goes to the split-K workspace, summed in split order by gemm_splitk_reduce_wide (gemm.hip).
+// [M][N] goes to the split-K workspace, summed in split order by gemm_splitk_reduce_wide (gemm_tile.hip).
 template <typename T, int FI, int FJ>
 __global__ __launch_bounds__(256) void gemm_skinny_kernel(const T* __restrict__ A, int64_t lda, int64_t M,
                                                           const T* __restrict__ B, int64_t ldb, int64_t N,
@@ -590,7 +590,8 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const T* __restrict__ 
 
 static int skinny_ks(int dtype) { return dtype == VS_BF16 ? 32 : 16; }
 
-bool skinny_ok(const vs_gemm_desc* d) {
+// the kernel's own limits (the shape, layouts and epilogues it is built for)
+static bool skinny_shape_ok(const vs_gemm_desc* d) {
   const uint32_t f = d->epilogue;
   const int ks = skinny_ks(d->dtype);
   const int vec = d->dtype == VS_BF16 ? 8 : 4;
@@ -618,6 +619,17 @@ size_t skinny_workspace_bytes(int32_t dtype, int64_t M, int64_t N, int64_t K) {
   int64_t sps;
   const int S = skinny_splits(K, ks, &sps);
   return (size_t)S * (size_t)(M * N) * 4;
+}
+
+// skinny split-K with K-contiguous operands (the head forward): fragments straight from HBM
+bool skinny_ok(const vs_gemm_desc* d) {
+  // the kernel and its reduce: no alpha, the partials in the caller's workspace, a dense C whose
+  // float4 (and the bias's) are 16-B aligned
+  const bool dense_c = d->ldc == d->N && aligned16(d->c) && (!(d->epilogue & VS_EPI_BIAS) || aligned16(d->bias));
+  const bool can = d->alpha == 1.0f && splitk_ws(d) && dense_c && skinny_shape_ok(d) &&
+                   (size_t)d->workspace_bytes >= skinny_workspace_bytes(d->dtype, d->M, d->N, d->K);
+  // knob: VSPIKE_NO_SKINNY
+  return can && !knob(VS_KNOB_NO_SKINNY);
 }
 
 template <typename T>
@@ -773,6 +785,18 @@ static void launch_dw_t(const bf16_t* a, int64_t lda, int64_t Ma, const bf16_t* 
   const int64_t blocks = (int64_t)tiles * (BM * BN / 256) + (sum_len + 1023) / 1024;
   hipLaunchKernelGGL((gemm_dw_reduce<BM, BN, TRANS>), dim3((unsigned)blocks), dim3(1024), 0, s, part, sums, p.g, Ma, Nb,
                      c, ldc, bias, sum_len, sum_tiles, (int)sum_w);
+}
+
+bool dw_ok(const vs_gemm_desc* d) {
+  // the kernel: dW = dY^T X with both bf16 operands token-major, 16-B rows and tiles; f32 C += the
+  // partials (reduced in a fixed order from the caller's workspace) and nothing else -- it does not
+  // scale by alpha, and an explicit split_k is the generic tiles' business
+  const bool can = d->alpha == 1.0f && d->dtype == VS_BF16 && d->out_dtype == VS_F32 && d->epilogue == VS_EPI_ATOMIC &&
+                   !d->a_kcontig && !d->b_kcontig && d->split_k <= 0 && splitk_ws(d) && d->K >= 1 && d->M % 8 == 0 &&
+                   d->N % 8 == 0 && d->lda % 8 == 0 && d->ldb % 8 == 0 &&
+                   (size_t)d->workspace_bytes >= dw_workspace_bytes(d->M, d->N, d->K);
+  // knob: VSPIKE_DW_OLD sends the product to the generic split-K tiles
+  return can && !knob(VS_KNOB_DW_OLD);
 }
 
 int launch_dw(const vs_gemm_desc* d, hipStream_t s) {
