@@ -31,7 +31,7 @@ extern "C" {
 /* element types */
 #define VS_F32 0
 #define VS_BF16 1
-#define VS_U8 2   /* raw video frames only (vs_video_preprocess) */
+#define VS_U8 2   /* raw video frames only (vs_video_preprocess, vs_pca_*, vs_contrast_frames, vs_rrr_pixel_*) */
 #define VS_F64 4  /* the RRR validation only (vs_rrr_*): y / gt as f64 */
 #define VS_FP8 3  /* OCP e4m3 with MX (E8M0 per 32 k) scales: vs_gemm_mxfp8 operands; as vs_vit_layer.dtype:
                      bf16 everywhere + MX-FP8 forward block products (BASELINE C5) */
@@ -617,6 +617,40 @@ int vs_gauss_smooth_time(int64_t K, int64_t T, int64_t N, const void* y, int32_t
                          int64_t radius, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The RRR baseline straight from the pixels (csrc/rrr_pixel.hip): src/train_rrr.py's
+ * input_mod 'whisker-video' for one session whose features are the C pixels of a frame.
+ *   X [K, F, C] dense, VS_U8 or VS_F32 (`x_dtype`): K trials of F frames, stored once and never standardised in
+ *   memory;  idx [T] int64 on the device: time bin t reads frame idx[t] (a value outside [0, F) is clamped into
+ *   it; vspike.ops checks the indices on the host);  mean, sd [F, C]: the statistics of the training trials, f64
+ *   for VS_U8 and f32 for VS_F32 (numpy's dtypes), as vs_rrr_pixel_stats writes them.
+ * The value that enters a product is (double(x) - mean) / sd for VS_U8 and the f32-rounded (x - mean) / sd,
+ * widened, for VS_F32, formed at the operand load with a true division; the bias column is an implicit 1.  The
+ * other operands, the results and the contracts are vs_rrr_wide_loss_grad's / vs_rrr_wide_score's: f64 products on
+ * the f64 MFMA, no atomics, bitwise repeatable, loss-only mode (dU = dV = db = NULL) gives the same loss bits.
+ * 1 <= C <= 32768, 1 <= r <= 4 (the gradient kernel keeps 2 x 16 r doubles per lane in registers), else VS_EINVAL
+ * before any launch.  No buffer of K T C, K F C or T C N elements exists.
+ * ------------------------------------------------------------------------------------------ */
+/* mean[f,c], sd[f,c] over the K trials with numpy's roundings: np.mean, np.std and np.clip(., 1e-8, None) of
+   X[:, f, c], bit for bit (VS_U8: f64, the integer sum exact; VS_F32: every step in f32). */
+int vs_rrr_pixel_stats(int64_t K, int64_t F, int64_t C, const void* X, int32_t x_dtype, void* mean, void* sd,
+                       void* stream);
+/* workspace (doubles, each piece rounded up to 256 bytes): K T N (residuals) + T ceil(N/256) + ceil(N (C + T) / 256)
+   (loss partials) + ceil((C+1)/64) ceil(N/64) r T (dV partials); 0.17 GB at K 400, T 100, N 512, C 18260, r 3.
+   0 outside the supported sizes. */
+size_t vs_rrr_pixel_loss_grad_workspace_bytes(int64_t K, int64_t T, int64_t N, int64_t C, int64_t r);
+int vs_rrr_pixel_loss_grad(int64_t K, int64_t F, int64_t T, int64_t N, int64_t C, int64_t r, const void* X,
+                           int32_t x_dtype, const int64_t* idx, const void* mean, const void* sd, const void* y,
+                           int32_t y_dtype, const double* U, const double* V, const double* b, double l2,
+                           double* loss, double* dU, double* dV, double* db, void* workspace, void* stream);
+/* workspace: that of vs_rrr_wide_score */
+size_t vs_rrr_pixel_score_workspace_bytes(int64_t K, int64_t T, int64_t N);
+int vs_rrr_pixel_score(int64_t K, int64_t F, int64_t T, int64_t N, int64_t C, int64_t r, const void* X,
+                       int32_t x_dtype, const int64_t* idx, const void* mean, const void* sd, const double* U,
+                       const double* V, const double* b, const double* mean_y, const double* std_y, const void* gt,
+                       int32_t gt_dtype, double* pred, double* bps, double* r2, double* out, void* workspace,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * PCA of a video by block subspace iteration (csrc/pca.hip): the kernels under
  * vspike.pca.PCA, which is get_pca_embedding (src/utils/utils.py:350-360) for the RRR baseline.
  *   X [M, D] row-major, rows dense, VS_U8 or VS_F32 (`x_dtype`): M frames of D pixels, stored once;
@@ -794,6 +828,12 @@ int vs_rrr_dispatch_counts(int64_t* out, int n);
 #define VS_PCA_PATH_GRAM    2   /* vs_pca_gram_apply */
 #define VS_PCA_PATH_COUNT   3
 int vs_pca_dispatch_counts(int64_t* out, int n);
+/* The pixel RRR entries' counters, one per call (vs_dispatch_reset zeroes them too): a group of their own for the
+   same reason. */
+#define VS_RRR_PIXEL_PATH_PRODUCT 0   /* vs_rrr_pixel_loss_grad / vs_rrr_pixel_score */
+#define VS_RRR_PIXEL_PATH_STATS   1   /* vs_rrr_pixel_stats */
+#define VS_RRR_PIXEL_PATH_COUNT   2
+int vs_rrr_pixel_dispatch_counts(int64_t* out, int n);
 /* 1 when every compiled instance of the 256 x 256 forward / dX GEMM (VS_PATH_GEMM_G256) has no private
    (scratch) segment: its early-DMA wait counts the epilogue's stores exactly.  An instance that spills
    falls back to vmcnt(0) on its own; this is the test's view of the same check. */
@@ -842,6 +882,7 @@ int vs_g256_scratch_free(void);
 #define VS_KNOB_DW256_ALL   36   /* 1: the 768 x 768 projection dW on the 256 x 256 dW kernel too (default: split-K dW tiles) */
 #define VS_KNOB_LN_FWD_BLOCKS 37 /* LayerNorm forward (vectorised) grid cap (0 = default 768) */
 #define VS_KNOB_G256_A3     35   /* 256 x 256 forward / dX GEMM: the streamed A operand in three LDS slots (DMA two stages ahead, counted stage wait): 0 / 1 = on (default), 2 = off (two slots, round 5) */
+#define VS_KNOB_RRR_PIXEL_RECIP 38 /* vs_rrr_pixel_*: 1 = standardise with a reciprocal multiply instead of the division (last-bit differences; A/B only) */
 #define VS_KNOB_COUNT       40
 int vs_knob_get(int knob);               /* VS_EINVAL for an unknown id */
 int vs_knob_set(int knob, int value);    /* returns the previous value; VS_EINVAL for an unknown id */

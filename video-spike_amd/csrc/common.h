@@ -51,6 +51,8 @@ void count_ln(int kernel, bool bwd);
 void count_rrr(int id);
 // PCA counters (VS_PCA_PATH_*, vs_pca_dispatch_counts)
 void count_pca(int id);
+// pixel RRR counters (VS_RRR_PIXEL_PATH_*, vs_rrr_pixel_dispatch_counts)
+void count_rrr_pixel(int id);
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

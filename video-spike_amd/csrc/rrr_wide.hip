@@ -34,6 +34,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "rrr_wide.h"
 
 namespace vs {
 
@@ -549,6 +550,28 @@ static RrwScoreWs rrw_score_ws(int64_t K, int64_t T, int64_t N) {
   return w;
 }
 
+size_t rrw_score_workspace_bytes(int64_t K, int64_t T, int64_t N) { return rrw_score_ws(K, T, N).total; }
+
+int rrw_score_yhat(hipStream_t s, int64_t K, int64_t T, int64_t N, const double* mean_y, const double* std_y,
+                   const void* gt, int32_t gt_dtype, double* pred, double* bps, double* r2, double* out,
+                   void* workspace) {
+  const RrwScoreWs w = rrw_score_ws(K, T, N);
+  const double* yhat = (const double*)((char*)workspace + w.yhat);
+  double* stat = (double*)((char*)workspace + w.stat);
+  const dim3 grid((unsigned)cdiv(N, 64), (unsigned)w.chunks);
+  if (gt_dtype == VS_F32)
+    hipLaunchKernelGGL(rrw_score_kernel<float>, grid, dim3(256), 0, s, K, T, N, w.kchunk, yhat, mean_y, std_y,
+                       (const float*)gt, pred, stat);
+  else
+    hipLaunchKernelGGL(rrw_score_kernel<double>, grid, dim3(256), 0, s, K, T, N, w.kchunk, yhat, mean_y, std_y,
+                       (const double*)gt, pred, stat);
+  VS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rrw_score_final_kernel, dim3(1), dim3(256), 0, s, K, T, N, w.chunks, (const double*)stat, bps, r2,
+                     out);
+  VS_LAUNCH_CHECK();
+  return VS_OK;
+}
+
 // ---- Gaussian smoothing along time -----------------------------------------------------------------------
 // scipy.ndimage.gaussian_filter1d(y, sigma, axis=1, mode='reflect'): the line is held in f64, the symmetric
 // kernel is applied as  acc = in[t] w[R];  acc = (in[t-j] + in[t+j]) w[R-j] + acc  for j = R .. 1  with the
@@ -660,24 +683,12 @@ extern "C" int vs_rrr_wide_score(int64_t K, int64_t T, int64_t N, int64_t C, int
   hipStream_t s = (hipStream_t)stream;
   const RrwScoreWs w = rrw_score_ws(K, T, N);
   double* yhat = (double*)((char*)workspace + w.yhat);
-  double* stat = (double*)((char*)workspace + w.stat);
   ScopedTimer timer(VS_TIMER_MISC, s,
                     (double)K * T * ((double)N * ((gt_dtype == VS_F32 ? 4.0 : 8.0) + (pred ? 8.0 : 0.0)) + (C + 1) * 8.0));
   count_rrr(VS_RRR_PATH_WIDE);
   rrw_launch_fwd<double, true>(s, K, T, N, (int)C, (int)r, X, nullptr, U, V, b, yhat);
   VS_LAUNCH_CHECK();
-  const dim3 grid((unsigned)cdiv(N, 64), (unsigned)w.chunks);
-  if (gt_dtype == VS_F32)
-    hipLaunchKernelGGL(rrw_score_kernel<float>, grid, dim3(256), 0, s, K, T, N, w.kchunk, (const double*)yhat, mean_y,
-                       std_y, (const float*)gt, pred, stat);
-  else
-    hipLaunchKernelGGL(rrw_score_kernel<double>, grid, dim3(256), 0, s, K, T, N, w.kchunk, (const double*)yhat, mean_y,
-                       std_y, (const double*)gt, pred, stat);
-  VS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rrw_score_final_kernel, dim3(1), dim3(256), 0, s, K, T, N, w.chunks, (const double*)stat, bps, r2,
-                     out);
-  VS_LAUNCH_CHECK();
-  return VS_OK;
+  return rrw_score_yhat(s, K, T, N, mean_y, std_y, gt, gt_dtype, pred, bps, r2, out, workspace);
 }
 
 extern "C" int vs_gauss_smooth_time(int64_t K, int64_t T, int64_t N, const void* y, int32_t dtype,

@@ -35,7 +35,7 @@ static const KnobDef kKnobs[VS_KNOB_COUNT] = {
     {"VSPIKE_LN_BLOCKS", 0},   {"VSPIKE_DH_F32", 0},       {"VSPIKE_NO_PATCH_FUSED", 0}, {"VSPIKE_NO_DW_GROUP", 0},
     {"VSPIKE_ATTN_VARIANT", 0}, {"VSPIKE_SLAB_WV", 0}, {"VSPIKE_WRES_WV", 0}, {"VSPIKE_WRES_DBG", 0}, {"VSPIKE_G256", 0}, {"VSPIKE_G256_GRID", 0}, {"VSPIKE_G256_DBG", 0}, {"VSPIKE_NO_DW256", 0}, {"VSPIKE_G256_STAGGER", 0}, {"VSPIKE_CONV_DW128", 0},
     {"VSPIKE_CONV_MFMA", 0}, {"VSPIKE_G256_A3", 0}, {"VSPIKE_DW256_ALL", 0}, {"VSPIKE_LN_FWD_BLOCKS", 0},
-    {nullptr, 0}};
+    {"VSPIKE_RRR_PIXEL_RECIP", 0}};
 static std::atomic<int> g_knob[VS_KNOB_COUNT];
 static std::once_flag g_knob_once;
 static void knob_init() {
@@ -59,6 +59,8 @@ static std::atomic<int64_t> g_rrr_dispatch[VS_RRR_PATH_COUNT];
 void count_rrr(int id) { g_rrr_dispatch[id].fetch_add(1, std::memory_order_relaxed); }
 static std::atomic<int64_t> g_pca_dispatch[VS_PCA_PATH_COUNT];
 void count_pca(int id) { g_pca_dispatch[id].fetch_add(1, std::memory_order_relaxed); }
+static std::atomic<int64_t> g_rrr_pixel_dispatch[VS_RRR_PIXEL_PATH_COUNT];
+void count_rrr_pixel(int id) { g_rrr_pixel_dispatch[id].fetch_add(1, std::memory_order_relaxed); }
 static std::atomic<int64_t> g_ln_dispatch[2 * VS_LN_KERNELS];
 void count_ln(int kernel, bool bwd) {
   g_ln_dispatch[(bwd ? VS_LN_KERNELS : 0) + kernel].fetch_add(1, std::memory_order_relaxed);
@@ -106,7 +108,8 @@ ScopedTimer::~ScopedTimer() {
 // 7: vs_vit_layer.next_ln_* / ln1_ready (the next block's LayerNorm1 in the fused MLP epilogue);
 // 10: vs_pca_* (csrc/pca.hip) and vs_pca_dispatch_counts
 // 11: vs_contrast_frames (csrc/contrast_loader.hip)
-extern "C" int vs_version(void) { return 11; }
+// 12: vs_rrr_pixel_* (csrc/rrr_pixel.hip) and vs_rrr_pixel_dispatch_counts
+extern "C" int vs_version(void) { return 12; }
 extern "C" const char* vs_build_id(void) { return VS_BUILD_ID; }
 
 extern "C" int vs_knob_get(int k) {
@@ -139,6 +142,7 @@ extern "C" int vs_dispatch_reset(void) {
   for (auto& c : vs::g_ln_dispatch) c.store(0, std::memory_order_relaxed);
   for (auto& c : vs::g_rrr_dispatch) c.store(0, std::memory_order_relaxed);
   for (auto& c : vs::g_pca_dispatch) c.store(0, std::memory_order_relaxed);
+  for (auto& c : vs::g_rrr_pixel_dispatch) c.store(0, std::memory_order_relaxed);
   return VS_OK;
 }
 extern "C" int vs_rrr_dispatch_counts(int64_t* out, int n) {
@@ -148,6 +152,11 @@ extern "C" int vs_rrr_dispatch_counts(int64_t* out, int n) {
 extern "C" int vs_pca_dispatch_counts(int64_t* out, int n) {
   for (int i = 0; i < n && i < VS_PCA_PATH_COUNT; ++i) out[i] = vs::g_pca_dispatch[i].load(std::memory_order_relaxed);
   return VS_PCA_PATH_COUNT;
+}
+extern "C" int vs_rrr_pixel_dispatch_counts(int64_t* out, int n) {
+  for (int i = 0; i < n && i < VS_RRR_PIXEL_PATH_COUNT; ++i)
+    out[i] = vs::g_rrr_pixel_dispatch[i].load(std::memory_order_relaxed);
+  return VS_RRR_PIXEL_PATH_COUNT;
 }
 extern "C" int vs_ln_dispatch_counts(int64_t* out, int n) {
   for (int i = 0; i < n && i < 2 * VS_LN_KERNELS; ++i) out[i] = vs::g_ln_dispatch[i].load(std::memory_order_relaxed);

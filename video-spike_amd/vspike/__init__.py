@@ -11,7 +11,7 @@ from .loss import InfoNCE, MSEMeanLoss, PoissonNLLMeanLoss, make_criterion, mse_
 from .optim import FusedAdamW
 from .pca import PCA, pca_embedding, pca_rrr_data
 from .r3d import R3D
-from .rrr import RRR, RRRGD, prepare_rrr_inputs, train_rrr, train_rrr_baseline
+from .rrr import RRR, RRRGD, PixelFeatures, pixel_rrr_data, prepare_rrr_inputs, train_rrr, train_rrr_baseline
 from .temporal import VideoMAETemporal
 from .vit import VideoMAE
 
@@ -26,6 +26,6 @@ NAME2MODEL = {
     "ContrastViT": ContrastViT,
 }
 
-__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "ContrastViT", "InfoNCE", "RRR", "train_rrr", "RRRGD", "prepare_rrr_inputs", "train_rrr_baseline", "PCA", "pca_embedding", "pca_rrr_data", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
+__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "ContrastViT", "InfoNCE", "RRR", "train_rrr", "RRRGD", "prepare_rrr_inputs", "train_rrr_baseline", "PixelFeatures", "pixel_rrr_data", "PCA", "pca_embedding", "pca_rrr_data", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
            "mse_mean", "MSEMeanLoss", "make_criterion",
            "DictConfig", "update_config", "config_from_kwargs", "load_run_config"]

@@ -46,7 +46,7 @@ EXTRA_PATH_NAMES = CONTRAST_PATH_NAMES
 KNOB_NAMES = ("dw_old", "no_skinny", "no_slab", "no_big", "no_wres", "wres_gbwd", "no_wslab", "wslab", "wslab_g",
               "panel", "no_panel", "panel_grid", "no_fullk", "no_ring", "no_lnf_fuse", "no_ln_fuse", "dw_bm", "dw_bn",
               "dw_splits", "dw_stages", "ln_blocks", "dh_f32", "no_patch_fused", "no_dw_group", "attn_variant", "slab_wv", "wres_wv", "wres_dbg",
-              "g256", "g256_grid", "g256_dbg", "no_dw256", "g256_stagger", "conv_dw128", "conv_mfma", "g256_a3", "dw256_all", "ln_fwd_blocks")
+              "g256", "g256_grid", "g256_dbg", "no_dw256", "g256_stagger", "conv_dw128", "conv_mfma", "g256_a3", "dw256_all", "ln_fwd_blocks", "rrr_pixel_recip")
 KNOB_COUNT = 40
 
 c_i32, c_i64, c_u32, c_f32, c_p, c_sz = (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float,
@@ -216,6 +216,14 @@ PROTOTYPES = {
                                          c_p, c_p, c_p, c_p, c_p, c_p]),
     "vs_gauss_smooth_time": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_i32, c_p, c_i64, c_p, c_p]),
     "vs_rrr_dispatch_counts": (ctypes.c_int, [ctypes.POINTER(c_i64), ctypes.c_int]),
+    "vs_rrr_pixel_stats": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_i32, c_p, c_p, c_p]),
+    "vs_rrr_pixel_loss_grad_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "vs_rrr_pixel_loss_grad": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i32, c_p, c_p, c_p, c_p,
+                                              c_i32, c_p, c_p, c_p, c_f64, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "vs_rrr_pixel_score_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "vs_rrr_pixel_score": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i32, c_p, c_p, c_p, c_p, c_p,
+                                          c_p, c_p, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "vs_rrr_pixel_dispatch_counts": (ctypes.c_int, [ctypes.POINTER(c_i64), ctypes.c_int]),
     "vs_pca_colmean_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vs_pca_colmean": (ctypes.c_int, [c_i64, c_i64, c_p, c_i32, c_p, c_p, c_p]),
     "vs_pca_project_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
@@ -364,6 +372,21 @@ def pca_dispatch_counts() -> dict:
     if total != n:
         raise VsError(f"PCA counters: the library has {total}, the binding names {n}")
     return {name: int(buf[i]) for i, name in enumerate(PCA_PATH_NAMES)}
+
+
+# vs_rrr_pixel_dispatch_counts' ids (vspike.h VS_RRR_PIXEL_PATH_*): a fourth group, for the same reason
+RRR_PIXEL_PATH_NAMES = ("rrr_pixel", "rrr_pixel_stats")
+
+
+def rrr_pixel_dispatch_counts() -> dict:
+    """Calls per pixel-RRR path since the last dispatch_reset(): "rrr_pixel" counts vs_rrr_pixel_loss_grad and
+    vs_rrr_pixel_score, "rrr_pixel_stats" vs_rrr_pixel_stats."""
+    n = len(RRR_PIXEL_PATH_NAMES)
+    buf = (c_i64 * n)()
+    total = lib().vs_rrr_pixel_dispatch_counts(buf, n)
+    if total != n:
+        raise VsError(f"pixel RRR counters: the library has {total}, the binding names {n}")
+    return {name: int(buf[i]) for i, name in enumerate(RRR_PIXEL_PATH_NAMES)}
 
 
 def total_path_count() -> int:

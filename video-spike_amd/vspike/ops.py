@@ -549,6 +549,113 @@ def rrr_wide_score(X, U, V, b, mean_y, std_y, gt, bps, r2, out, pred=None, works
     return out
 
 
+# ---- the RRR baseline straight from the pixels (csrc/rrr_pixel.hip): X [K, F, C] uint8 / float32, stored once ----
+RRR_PIXEL_MAX_FEATURES, RRR_PIXEL_MAX_COMPONENTS = 32768, 4
+
+
+def _rrr_pixel_x(X, what):
+    require_device(X)
+    if X.dim() != 3 or X.dtype not in (torch.uint8, torch.float32) or not X.is_contiguous():
+        raise L.VsError(f"{what}: X [K, F, C] dense uint8 / float32")
+    return L.VS_U8 if X.dtype == torch.uint8 else L.VS_F32
+
+
+def _rrr_pixel_dims(X, idx, mean, std, y, U, V, b, what):
+    """(K, F, T, N, C, r, x dtype code) of the pixel RRR operands after checking them: X [K, F, C] uint8 / float32,
+    idx [T] int64 frame indices on the device, mean / std [F, C] float64 (uint8 X) or float32 (float32 X),
+    y [K, T, N] float32 / float64, U [N, C, r], V [r, T], b [N, 1, T] float64, all dense."""
+    code = _rrr_pixel_x(X, what)
+    K, F, C = X.shape
+    stat = torch.float64 if X.dtype == torch.uint8 else torch.float32
+    N, Cu, r = U.shape
+    T = V.shape[1] if V.dim() == 2 else -1
+    ok = (Cu == C and tuple(y.shape) == (K, T, N) and tuple(V.shape) == (r, T) and b.numel() == N * T
+          and y.dtype in (torch.float32, torch.float64) and idx.dtype == torch.int64 and tuple(idx.shape) == (T,)
+          and all(tuple(t.shape) == (F, C) and t.dtype == stat for t in (mean, std))
+          and all(t.dtype == torch.float64 for t in (U, V, b))
+          and all(t.is_contiguous() for t in (idx, mean, std, y, U, V, b)))
+    if not ok:
+        raise L.VsError(f"{what}: X [K, F, C] uint8 / float32, idx [T] int64, mean / std [F, C] float64 (uint8 X) or "
+                        "float32 (float32 X), U [N, C, r], V [r, T], b [N, 1, T] dense float64 and y [K, T, N] dense "
+                        "float32 / float64")
+    return K, F, T, N, C, r, code
+
+
+def rrr_pixel_stats(X, mean=None, std=None):
+    """(mean, std) [F, C] over the trials of X [K, F, C] uint8 / float32 with numpy's roundings: np.mean, np.std
+    and np.clip(., 1e-8, None) along axis 0, bit for bit (vs_rrr_pixel_stats).  float64 for uint8 X, float32 for
+    float32 X, as numpy gives them."""
+    code = _rrr_pixel_x(X, "rrr_pixel_stats")
+    K, F, C = X.shape
+    stat = torch.float64 if X.dtype == torch.uint8 else torch.float32
+    if mean is None:
+        mean = torch.empty(F, C, dtype=stat, device=X.device)
+    if std is None:
+        std = torch.empty(F, C, dtype=stat, device=X.device)
+    require_device(mean, std)
+    for t in (mean, std):
+        if tuple(t.shape) != (F, C) or t.dtype != stat or not t.is_contiguous():
+            raise L.VsError("rrr_pixel_stats: mean / std are dense [F, C], float64 for uint8 X and float32 for float32 X")
+    check(lib().vs_rrr_pixel_stats(K, F, C, X.data_ptr(), code, mean.data_ptr(), std.data_ptr(), stream()),
+          "vs_rrr_pixel_stats")
+    return mean, std
+
+
+def rrr_pixel_loss_grad_workspace_bytes(K, T, N, C, r):
+    return int(lib().vs_rrr_pixel_loss_grad_workspace_bytes(K, T, N, C, r))
+
+
+def rrr_pixel_loss_grad(X, idx, mean, std, y, U, V, b, l2, loss, dU=None, dV=None, db=None, workspace=None):
+    """rrr_wide_loss_grad for one session whose features are the pixels of X [K, F, C] uint8 / float32, 1 <= C <=
+    32768 (vs_rrr_pixel_loss_grad): time bin t reads frame idx[t], standardised with mean / std [F, C] at the
+    operand load; the bias column is implicit.  The same results and checks; 1 <= r <= 4.  The caller guarantees
+    0 <= idx < F (PixelFeatures checks it once); the kernel clamps."""
+    require_device(X, idx, mean, std, y, U, V, b, loss, dU, dV, db, workspace)
+    K, F, T, N, C, r, code = _rrr_pixel_dims(X, idx, mean, std, y, U, V, b, "rrr_pixel_loss_grad")
+    for g, ref in ((dU, U), (dV, V), (db, b)):
+        if g is not None and (g.numel() != ref.numel() or g.dtype != torch.float64 or not g.is_contiguous()):
+            raise L.VsError("rrr_pixel_loss_grad: dU / dV / db are dense float64 of the shapes of U / V / b")
+    if loss.dtype != torch.float64 or loss.numel() < 1:
+        raise L.VsError("rrr_pixel_loss_grad: loss must hold one float64")
+    need = rrr_pixel_loss_grad_workspace_bytes(K, T, N, C, r)
+    if workspace is None:
+        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise L.VsError("rrr_pixel_loss_grad: workspace too small")
+    check(lib().vs_rrr_pixel_loss_grad(K, F, T, N, C, r, X.data_ptr(), code, idx.data_ptr(), mean.data_ptr(),
+                                       std.data_ptr(), y.data_ptr(), _f64_code(y), U.data_ptr(), V.data_ptr(),
+                                       b.data_ptr(), float(l2), loss.data_ptr(), ptr(dU), ptr(dV), ptr(db),
+                                       workspace.data_ptr(), stream()), "vs_rrr_pixel_loss_grad")
+    return loss
+
+
+def rrr_pixel_score_workspace_bytes(K, T, N):
+    return int(lib().vs_rrr_pixel_score_workspace_bytes(K, T, N))
+
+
+def rrr_pixel_score(X, idx, mean, std, U, V, b, mean_y, std_y, gt, bps, r2, out, pred=None, workspace=None):
+    """rrr_wide_score for pixel features (vs_rrr_pixel_score): the operands of rrr_pixel_loss_grad, the results
+    and checks of rrr_wide_score."""
+    require_device(X, idx, mean, std, U, V, b, mean_y, std_y, gt, bps, r2, out, pred, workspace)
+    K, F, T, N, C, r, code = _rrr_pixel_dims(X, idx, mean, std, gt, U, V, b, "rrr_pixel_score")
+    for t, numel in ((mean_y, T * N), (std_y, T * N), (bps, N), (r2, N), (pred, K * T * N)):
+        if t is not None and (t.numel() != numel or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise L.VsError("rrr_pixel_score: mean_y / std_y [T, N], bps / r2 [N], pred [K, T, N] dense float64")
+    if out.dtype != torch.float64 or out.numel() < 2:
+        raise L.VsError("rrr_pixel_score: out must hold two float64")
+    need = rrr_pixel_score_workspace_bytes(K, T, N)
+    if workspace is None:
+        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise L.VsError("rrr_pixel_score: workspace too small")
+    check(lib().vs_rrr_pixel_score(K, F, T, N, C, r, X.data_ptr(), code, idx.data_ptr(), mean.data_ptr(),
+                                   std.data_ptr(), U.data_ptr(), V.data_ptr(), b.data_ptr(), mean_y.data_ptr(),
+                                   std_y.data_ptr(), gt.data_ptr(), _f64_code(gt), ptr(pred), bps.data_ptr(),
+                                   r2.data_ptr(), out.data_ptr(), workspace.data_ptr(), stream()),
+          "vs_rrr_pixel_score")
+    return out
+
+
 def gauss_weights(sigma):
     """(weights float64 [2 radius + 1], radius) of scipy.ndimage.gaussian_filter1d(., sigma) with its default
     truncate = 4, computed as scipy's _gaussian_kernel1d does."""

@@ -17,7 +17,9 @@ they come in (float32 in the reference's use).
 The RRR baseline `src/train_rrr.py` is the second half of this module: `RRRGD` (the reference's model with its
 sessions sharing V; inputs up to 1024 features run `vs_rrr_wide_loss_grad` / `vs_rrr_wide_score`, csrc/rrr_wide.hip),
 `prepare_rrr_inputs` (Gaussian smoothing, one-hot choice / block, standardisation, frame selection) and
-`train_rrr_baseline`.
+`train_rrr_baseline`.  Raw pixels ('whisker-video': more than 1024 features, up to 32768) go in as `PixelFeatures`,
+a view of the video in its own dtype with the training statistics; such sessions run `vs_rrr_pixel_loss_grad` /
+`vs_rrr_pixel_score` (csrc/rrr_pixel.hip), which standardise at the operand load.
 """
 from __future__ import annotations
 
@@ -203,6 +205,18 @@ def _device_tensor(a, device):
     return t.to(device)
 
 
+def _device_video(a, device):
+    """'whisker-video' frames on the device: (K, F, c, h, w) flattened to (K, F, c h w) as a view
+    (train_rrr.py:99-102).  More than 1024 pixels per frame stay in their dtype; narrower ones go through
+    `_device_tensor` as every other input does."""
+    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+    if t.dim() == 5:
+        t = t.reshape(t.shape[0], t.shape[1], -1)
+    if t.dim() == 3 and t.shape[2] > WIDE_MAX_FEATURES:
+        return t.to(device).contiguous()
+    return _device_tensor(t, device)
+
+
 def train_rrr(data_dict: dict, device=None, n_comp: int = 3, l2: float = 100.) -> dict:
     """`train_rrr` of src/utils/utils.py:376-456: data_dict[eid] = {'X': [train, val] (K, T, C), 'y': [train,
     val] (K, T, N), 'setup': {}}, numpy or torch.  Per eid: standardise X and y with the train split's
@@ -242,7 +256,7 @@ INPUT_MODS = ("me", "of", "of-2d", "of-2d-v", "all", "other", "me-all", "of-all"
 def check_dims_wide(C: int, r: int) -> None:
     if not 1 <= C <= WIDE_MAX_FEATURES:
         raise VsError(f"RRRGD: {C} features, supported 1..{WIDE_MAX_FEATURES} (the bias column not counted); "
-                      "raw pixel inputs ('whisker-video') are out of scope")
+                      "wider inputs (raw pixels, 'whisker-video') go in as vspike.rrr.PixelFeatures")
     if not 1 <= r <= MAX_COMPONENTS:
         raise VsError(f"RRRGD: {r} components, supported 1..{MAX_COMPONENTS}")
 
@@ -251,11 +265,69 @@ def _is_wide(C: int) -> bool:
     return C > MAX_FEATURES
 
 
+PIXEL_MAX_FEATURES, PIXEL_MAX_COMPONENTS = ops.RRR_PIXEL_MAX_FEATURES, ops.RRR_PIXEL_MAX_COMPONENTS
+
+
+def check_dims_pixel(C: int, r: int) -> None:
+    if not 1 <= C <= PIXEL_MAX_FEATURES:
+        raise VsError(f"RRRGD: {C} pixels per frame, supported 1..{PIXEL_MAX_FEATURES}")
+    if not 1 <= r <= PIXEL_MAX_COMPONENTS:
+        raise VsError(f"RRRGD: {r} components, supported 1..{PIXEL_MAX_COMPONENTS} for pixel features (the gradient "
+                      "kernel keeps U and dU of its tile in registers)")
+
+
+class PixelFeatures:
+    """A session's features as raw pixels: X_raw [K, F, C] uint8 or float32 (or [K, F, c, h, w], flattened as
+    train_rrr.py:99-102 does) is kept as it is, a view and never a copy; time bin t reads frame idx[t]; mean / std
+    [F, C] are the training trials' statistics (`ops.rrr_pixel_stats`: float64 for uint8, float32 for float32, as
+    numpy gives them).  It stands where RRRGD takes a standardised float64 X [K, T, C+1]: the kernels form
+    (x - mean) / std at the operand load and the bias column is implicit.  `shape` is that tensor's shape."""
+
+    def __init__(self, X_raw: torch.Tensor, idx, mean: torch.Tensor, std: torch.Tensor):
+        if not torch.is_tensor(X_raw) or X_raw.dim() not in (3, 5) or X_raw.dtype not in (torch.uint8, torch.float32):
+            raise VsError("PixelFeatures: X_raw [K, F, C] (or [K, F, c, h, w]) uint8 / float32 tensor")
+        if not X_raw.is_contiguous():
+            raise VsError("PixelFeatures: X_raw must be dense (it is used in place, never copied)")
+        X = X_raw.view(X_raw.shape[0], X_raw.shape[1], -1)
+        K, F, C = X.shape
+        ix = idx.detach().cpu().numpy() if torch.is_tensor(idx) else np.asarray(idx)
+        if ix.ndim != 1 or ix.dtype.kind not in "iu" or len(ix) < 1:
+            raise VsError("PixelFeatures: idx must hold the frame index of every time bin (integers)")
+        if ix.min() < 0 or ix.max() >= F:
+            raise VsError(f"PixelFeatures: idx must hold frame indices below {F}")
+        stat = torch.float64 if X.dtype == torch.uint8 else torch.float32
+        for t in (mean, std):
+            if not torch.is_tensor(t) or tuple(t.shape) != (F, C) or t.dtype != stat:
+                raise VsError(f"PixelFeatures: mean / std must be [F, C] = [{F}, {C}] tensors of {stat} "
+                              f"(the statistics numpy gives for {X.dtype})")
+        self.X, self.mean, self.std = X, mean.contiguous(), std.contiguous()
+        self.idx = torch.from_numpy(ix.astype(np.int64)).to(X.device)
+        self.shape = torch.Size((K, len(ix), C + 1))
+        self.device = X.device
+
+    def materialise(self) -> torch.Tensor:
+        """The float64 X [K, T, C+1] this object stands for, in the kernels' arithmetic (tests and small inputs
+        only: it is the buffer the pixel entries exist to avoid)."""
+        x = self.X.index_select(1, self.idx)
+        m, s = self.mean.index_select(0, self.idx), self.std.index_select(0, self.idx)
+        z = (x.double() - m) / s if self.X.dtype == torch.uint8 else _div(x - m, s).double()
+        return torch.cat([z, torch.ones(z.shape[0], z.shape[1], 1, dtype=torch.float64, device=z.device)], dim=2)
+
+
+def _pixel_call(fn):
+    """An ops.rrr_pixel_* entry with the leading operand of its wide counterpart."""
+    def call(X, *args, **kw):
+        return fn(X.X, X.idx, X.mean, X.std, *args, **kw)
+    return call
+
+
 class RRRGD:
     """The reference's RRRGD with its sessions (src/model/rrr.py:29-202): every session has its own U [N, C, r] and
     b [N, 1, T]; one V [r, T] is shared by all.  `fit({eid: (X, y)})` takes standardised device tensors per
     session, X [K, T, C+1] float64 with a last column of ones and y [K, T, N] float32 or float64; T is common,
-    K, N and C may differ.  Sessions with C <= 32 run vs_rrr_loss_grad, wider ones vs_rrr_wide_loss_grad."""
+    K, N and C may differ.  Sessions with C <= 32 run vs_rrr_loss_grad, wider ones vs_rrr_wide_loss_grad.  A
+    session's X may instead be a PixelFeatures (raw pixels, C <= 32768, n_comp <= 4): it runs
+    vs_rrr_pixel_loss_grad / vs_rrr_pixel_score, and pixel, wide and narrow sessions mix in one fit."""
 
     def __init__(self, n_comp: int = 3, l2: float = 100.):
         self.n_comp, self.l2 = int(n_comp), float(l2)
@@ -263,6 +335,14 @@ class RRRGD:
         self.losses, self.n_iter, self.func_evals = [], 0, 0
 
     def _check(self, X, y, what="RRRGD"):
+        if isinstance(X, PixelFeatures):
+            if not torch.is_tensor(y) or y.dim() != 3 or X.shape[:2] != y.shape[:2] or y.device != X.device:
+                raise VsError(f"{what}: PixelFeatures of [K, F, C] pixels with T frame indices and y [K, T, N] on "
+                              "its device")
+            check_dims_pixel(X.shape[2] - 1, self.n_comp)
+            if y.dtype not in (torch.float32, torch.float64):
+                raise VsError(f"{what}: y must be float32 or float64")
+            return
         if not (torch.is_tensor(X) and torch.is_tensor(y)) or X.dim() != 3 or y.dim() != 3 \
                 or X.shape[:2] != y.shape[:2]:
             raise VsError(f"{what}: X [K, T, C+1] and y [K, T, N] device tensors per session")
@@ -283,7 +363,7 @@ class RRRGD:
         sess = {}
         for eid, (X, y) in data.items():
             self._check(X, y)
-            sess[eid] = (X.contiguous(), y.contiguous())
+            sess[eid] = (X if isinstance(X, PixelFeatures) else X.contiguous(), y.contiguous())
         Ts = {X.shape[1] for X, _ in sess.values()}
         if len(Ts) != 1:
             raise VsError(f"RRRGD.fit: the sessions share V, so T must be equal across them (got {sorted(Ts)})")
@@ -305,8 +385,12 @@ class RRRGD:
             dVs[eid] = torch.zeros(r, T, dtype=torch.float64, device=dev)
             U[eid].grad, b_master[eid].grad = dU[eid], torch.zeros_like(b_master[eid])
             wide = _is_wide(C)
-            fn[eid] = ops.rrr_wide_loss_grad if wide else ops.rrr_loss_grad
-            need = (ops.rrr_wide_loss_grad_workspace_bytes if wide else ops.rrr_loss_grad_workspace_bytes)(K, T, N, C)
+            if isinstance(X, PixelFeatures):
+                fn[eid] = _pixel_call(ops.rrr_pixel_loss_grad)
+                need = ops.rrr_pixel_loss_grad_workspace_bytes(K, T, N, C, r)
+            else:
+                fn[eid] = ops.rrr_wide_loss_grad if wide else ops.rrr_loss_grad
+                need = (ops.rrr_wide_loss_grad_workspace_bytes if wide else ops.rrr_loss_grad_workspace_bytes)(K, T, N, C)
             ws[eid] = torch.empty(need // 8 + 2, dtype=torch.float64, device=dev)
         V = torch.from_numpy(V0).to(dev).requires_grad_(True)
         V.grad = torch.zeros_like(V)
@@ -375,8 +459,12 @@ class RRRGD:
         for eid, (X, y) in data.items():
             self._check_session(eid, X, y, "RRRGD.mse")
             loss = torch.empty(1, dtype=torch.float64, device=X.device)
-            fn = ops.rrr_wide_loss_grad if _is_wide(X.shape[2] - 1) else ops.rrr_loss_grad
-            fn(X.contiguous(), y.contiguous(), self._U[eid], self._V, self._b[eid], 0.0, loss)
+            if isinstance(X, PixelFeatures):
+                fn = _pixel_call(ops.rrr_pixel_loss_grad)
+            else:
+                fn = ops.rrr_wide_loss_grad if _is_wide(X.shape[2] - 1) else ops.rrr_loss_grad
+                X = X.contiguous()
+            fn(X, y.contiguous(), self._U[eid], self._V, self._b[eid], 0.0, loss)
             total = loss if total is None else total + loss
         if total is None:
             raise VsError("RRRGD.mse: {eid: (X, y)} with at least one session")
@@ -392,8 +480,12 @@ class RRRGD:
         pred = torch.empty(K, T, N, dtype=torch.float64, device=dev) if want_pred else None
         bps, r2 = (torch.empty(N, dtype=torch.float64, device=dev) for _ in range(2))
         out = torch.empty(2, dtype=torch.float64, device=dev)
-        fn = ops.rrr_wide_score if _is_wide(X.shape[2] - 1) else ops.rrr_score
-        fn(X.contiguous(), self._U[eid], self._V, self._b[eid], mean_y.to(torch.float64).contiguous(),
+        if isinstance(X, PixelFeatures):
+            fn = _pixel_call(ops.rrr_pixel_score)
+        else:
+            fn = ops.rrr_wide_score if _is_wide(X.shape[2] - 1) else ops.rrr_score
+            X = X.contiguous()
+        fn(X, self._U[eid], self._V, self._b[eid], mean_y.to(torch.float64).contiguous(),
            std_y.to(torch.float64).contiguous(), gt.contiguous(), bps, r2, out, pred=pred)
         return {"pred": pred, "bps": bps, "r2": r2, "co_bps": out[0], "r2_mean": out[1]}
 
@@ -425,7 +517,12 @@ def prepare_rrr_inputs(data: dict, input_mod: str, idx=None, smooth_w=2, device=
     the bias column is appended and the T frames `idx` of F are selected (default: the reference's draw
     sort(choice(F - 1, T, replace=False)) from numpy's global generator, once for all sessions).
     Returns (prepared, ground_truth): prepared[eid] = {'X': [..], 'y': [..], 'setup': {mean_X_Tv, std_X_Tv,
-    mean_y_TN, std_y_TN}} as device tensors, ground_truth[eid] the raw validation counts."""
+    mean_y_TN, std_y_TN}} as device tensors, ground_truth[eid] the raw validation counts.
+    'whisker-video': X may be (K, F, c, h, w) and is flattened to (K, F, c h w) as a view (train_rrr.py:99-102).  A
+    session with more than 1024 pixels per frame comes back as PixelFeatures for both splits: X stays on the
+    device in its own dtype, uint8 or float32 (uint8 is NOT converted to float32 here, unlike narrower integer
+    inputs, which `_device_tensor` converts as before; numpy's statistics of a uint8 array are float64, and so are
+    these), the statistics come from vs_rrr_pixel_stats, and nothing of the video's size is written."""
     if input_mod not in INPUT_MODS:
         raise VsError(f"prepare_rrr_inputs: input_mod {input_mod!r} is none of {INPUT_MODS}")
     if not isinstance(data, dict) or not data:
@@ -434,11 +531,17 @@ def prepare_rrr_inputs(data: dict, input_mod: str, idx=None, smooth_w=2, device=
     loaded = {}
     for eid in eids:
         d = data[eid]
-        X = [_device_tensor(x, device or (x.device if torch.is_tensor(x) and x.is_cuda else "cuda")) for x in d["X"]]
+        X = [_device_video(x, device or (x.device if torch.is_tensor(x) and x.is_cuda else "cuda"))
+             if input_mod == "whisker-video" else
+             _device_tensor(x, device or (x.device if torch.is_tensor(x) and x.is_cuda else "cuda")) for x in d["X"]]
         y = [_device_tensor(v, X[0].device) for v in d["y"]]
         if any(x.dim() != 3 for x in X) or any(v.dim() != 3 for v in y) or X[0].shape[1:] != X[1].shape[1:] \
                 or y[0].shape[1:] != y[1].shape[1:] or any(x.shape[0] != v.shape[0] for x, v in zip(X, y)):
             raise VsError(f"prepare_rrr_inputs: session {eid!r}: X [K, F, C] and y [K, T, N] per split")
+        if input_mod == "whisker-video" and X[0].shape[2] > WIDE_MAX_FEATURES \
+                and (X[0].dtype != X[1].dtype or X[0].dtype not in (torch.uint8, torch.float32)):
+            raise VsError(f"prepare_rrr_inputs: session {eid!r}: more than {WIDE_MAX_FEATURES} pixels per frame need "
+                          "uint8 or float32 frames, the same dtype in both splits")
         loaded[eid] = (X, y)
     Ts = {y[0].shape[1] for _, y in loaded.values()}
     if len(Ts) != 1:
@@ -480,14 +583,18 @@ def prepare_rrr_inputs(data: dict, input_mod: str, idx=None, smooth_w=2, device=
                               "shape error at the standardisation)")
             X = new
         y = [ops.gauss_smooth_time(v.contiguous(), smooth_w) for v in y]         # train_rrr.py:118
-        mean_X, std_X = _std(X[0])                                               # train_rrr.py:144-145
+        pixels = input_mod == "whisker-video" and X[0].shape[2] > WIDE_MAX_FEATURES
+        mean_X, std_X = ops.rrr_pixel_stats(X[0]) if pixels else _std(X[0])      # train_rrr.py:144-145
         mean_y, std_y = _std(y[0])
         sel = torch.from_numpy(idx.astype(np.int64)).to(dev)
         Xs, ys = [], []
         for i in range(2):
-            x = _div(X[i] - mean_X, std_X).to(torch.float64)
-            ones = torch.ones(x.shape[0], x.shape[1], 1, dtype=torch.float64, device=dev)
-            Xs.append(torch.cat([x, ones], dim=2).index_select(1, sel).contiguous())   # train_rrr.py:156-163
+            if pixels:
+                Xs.append(PixelFeatures(X[i], idx, mean_X, std_X))
+            else:
+                x = _div(X[i] - mean_X, std_X).to(torch.float64)
+                ones = torch.ones(x.shape[0], x.shape[1], 1, dtype=torch.float64, device=dev)
+                Xs.append(torch.cat([x, ones], dim=2).index_select(1, sel).contiguous())   # train_rrr.py:156-163
             ys.append(_div(y[i] - mean_y, std_y))
         setup = dict(mean_X_Tv=mean_X, std_X_Tv=std_X, mean_y_TN=mean_y, std_y_TN=std_y)
         if isinstance(data[eid].get("setup"), dict):
@@ -518,3 +625,13 @@ def train_rrr_baseline(data: dict, input_mod: str, idx=None, n_comp: int = 3, l2
         result[eid] = {"gt": gt.cpu().numpy(), "pred": s["pred"].cpu().numpy(), "co_bps": s["bps"].cpu().tolist(),
                        "r2": s["r2"].cpu().tolist(), "eid": eid}
     return result, float(np.mean(test_bps))
+
+
+def pixel_rrr_data(train_X, train_y, test_X, test_y, eid: str = "session") -> dict:
+    """The dict `train_rrr_baseline(., 'whisker-video')` takes, from two videos (K, F, h w) or (K, F, c, h, w),
+    uint8 or float32, numpy or torch, and the binned spikes (K, T, N) of the same trials, like pca.pca_rrr_data.
+    Nothing is copied or converted here."""
+    for X, y in ((train_X, train_y), (test_X, test_y)):
+        if len(X.shape) not in (3, 5) or len(y.shape) != 3 or X.shape[0] != y.shape[0]:
+            raise VsError("pixel_rrr_data: videos (K, F, h w) or (K, F, c, h, w) and spikes (K, T, N) of the same trials")
+    return {eid: {"X": [train_X, test_X], "y": [train_y, test_y], "setup": {}}}
