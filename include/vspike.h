@@ -709,6 +709,36 @@ int vs_contrast_frames(int32_t in_dtype, int64_t F, int64_t H, int64_t W, const 
 int vs_contrast_frames_plan(int64_t H, int64_t W, int64_t S, int32_t* out);
 
 /* ------------------------------------------------------------------------------------------
+ * Behaviour features of the RRR baselines (csrc/flow_features.hip): the per-frame scalars the reference's
+ * get_optic_flow (src/utils/ibl_data_utils.py:1103-1243) and get_rrr_data (src/utils/utils.py:226-304) take from a
+ * dense flow field and the video.  flow is [trials][F - 1][H W][2] f32, dense; 1 <= H W <= 2^20 everywhere.
+ * Order statistics are exact (MSB-first radix select on order-preserving uint32 keys); counts use integer atomics,
+ * sums are f64 in an order fixed by the extents: equal inputs give equal bits.
+ * ------------------------------------------------------------------------------------------ */
+/* out[frame][c] = np.median over (h, w) of flow[frame][:, c] (absolute = 0) or of its |.| (absolute = 1): for an
+   even H W the f32 mean (a + b) / 2 of the two middle elements; NaN if that component of the frame holds a NaN.
+   The keys of both components are staged in LDS while H W <= vs_flow_plan's out[0]; larger frames are re-read. */
+int vs_flow_median2(int64_t frames, int64_t HW, const float* flow, int32_t absolute, float* out, void* stream);
+/* bounds[trial][c] = {np.percentile(x, q_lo), np.percentile(x, q_hi)} of x = |flow[trial][..., c]| (n = Fp H W < 2^31
+   values, f32), method "linear" with numpy 2's roundings for a scalar q: the quantile q / 100, the virtual index
+   (n - 1) q and the weight are f32, _lerp is f32.  stats (may be NULL) [trial][c][4] = the order statistics the two
+   are interpolated between.  A trial with a NaN gives NaN bounds.  K <= 65535.  workspace: 16-byte aligned,
+   vs_flow_quantiles_workspace_bytes(K) (0 for an unsupported K), need not be cleared. */
+size_t vs_flow_quantiles_workspace_bytes(int64_t K);
+int vs_flow_quantiles(int64_t K, int64_t Fp, int64_t HW, const float* flow, float q_lo, float q_hi, float* bounds,
+                      float* stats, void* workspace, void* stream);
+/* out[trial][f] = mean over (h, w, c) of clip(|flow[trial][f][., c]|, bounds[trial][c][0], bounds[trial][c][1]):
+   an f64 sum rounded once.  A NaN bound gives NaN. */
+int vs_flow_clip_mean(int64_t K, int64_t Fp, int64_t HW, const float* flow, const float* bounds, float* out,
+                      void* stream);
+/* out[trial][f] = mean over the pixels of |video[trial][f + 1] - video[trial][f]|, f = 0 .. F - 2; video
+   [trials][F][H W] VS_U8 (integer differences, an exact sum) or VS_F32 (f32 differences, f64 sum), read in place. */
+int vs_motion_energy(int32_t in_dtype, int64_t K, int64_t F, int64_t HW, const void* video, float* out, void* stream);
+/* out[0..2] = the largest H W whose keys vs_flow_median2 stages in LDS, the pixels one workgroup of
+   vs_flow_quantiles counts per pass, vs_flow_median2's threads per workgroup: what a test places its sizes by */
+int vs_flow_plan(int32_t* out);
+
+/* ------------------------------------------------------------------------------------------
  * Trial shards (host side of the input path; replaces the per-trial webdataset tars of
  * src/prepare_data.py:210-235 read by src/loader/base.py:21-41).  Fixed-size records: raw uint8
  * frames (T, C, H, W) + f32 spike counts (ap_rows, ap_cols) + a 64-byte "<eid>_<trial>" key.

@@ -4,6 +4,7 @@ Drop-in surface (src/utils/utils.py:28-34 of the reference): `NAME2MODEL[config.
 builds the plugin from `config.model`; `forward(inputs) -> log-rates (B, 100, N)`.  All compute
 runs in libvspike.so (hand-written HIP, include/vspike.h) — there is no CPU fallback.
 """
+from .behaviour import behaviour_rrr_data, flow_features, get_rrr_data
 from .contrast import ContrastViT
 from .config import DictConfig, config_from_kwargs, load_run_config, update_config
 from .linear import Linear
@@ -26,6 +27,6 @@ NAME2MODEL = {
     "ContrastViT": ContrastViT,
 }
 
-__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "ContrastViT", "InfoNCE", "RRR", "train_rrr", "RRRGD", "prepare_rrr_inputs", "train_rrr_baseline", "PixelFeatures", "pixel_rrr_data", "PCA", "pca_embedding", "pca_rrr_data", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
+__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "ContrastViT", "InfoNCE", "RRR", "train_rrr", "RRRGD", "prepare_rrr_inputs", "train_rrr_baseline", "PixelFeatures", "pixel_rrr_data", "PCA", "pca_embedding", "pca_rrr_data", "flow_features", "get_rrr_data", "behaviour_rrr_data", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
            "mse_mean", "MSEMeanLoss", "make_criterion",
            "DictConfig", "update_config", "config_from_kwargs", "load_run_config"]

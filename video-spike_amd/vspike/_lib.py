@@ -236,6 +236,12 @@ PROTOTYPES = {
     "vs_contrast_frames": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, ctypes.c_float,
                                           ctypes.c_float, c_p, c_p, c_i32, c_p]),
     "vs_contrast_frames_plan": (ctypes.c_int, [c_i64, c_i64, c_i64, ctypes.POINTER(c_i32)]),
+    "vs_flow_median2": (ctypes.c_int, [c_i64, c_i64, c_p, c_i32, c_p, c_p]),
+    "vs_flow_quantiles_workspace_bytes": (c_sz, [c_i64]),
+    "vs_flow_quantiles": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_f32, c_f32, c_p, c_p, c_p, c_p]),
+    "vs_flow_clip_mean": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
+    "vs_motion_energy": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
+    "vs_flow_plan": (ctypes.c_int, [ctypes.POINTER(c_i32)]),
     "vs_timing_enable": (ctypes.c_int, [ctypes.c_int]),
     "vs_timing_collect": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double)]),
     "vs_timing_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),

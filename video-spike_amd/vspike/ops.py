@@ -928,3 +928,89 @@ def contrast_frames(video, idx, size=144, mean=0.5, std=0.5, out=None, check_idx
     if G:
         _CONTRAST_TABLES[key] = table
     return out
+
+
+# ---- behaviour features of the RRR baselines (csrc/flow_features.hip) ----
+FLOW_MAX_PIXELS = 1 << 20
+
+
+def flow_plan() -> dict:
+    """The sizes at which the flow kernels change path (vs_flow_plan): `stage_max`, the largest H W whose keys
+    flow_median2 keeps in LDS; `quantile_chunk`, the pixels one workgroup of flow_quantiles counts per pass."""
+    buf = (L.c_i32 * 3)()
+    check(lib().vs_flow_plan(buf), "vs_flow_plan")
+    return {"stage_max": int(buf[0]), "quantile_chunk": int(buf[1]), "median_threads": int(buf[2])}
+
+
+def _flow_dims(flow, what):
+    """(K, F - 1, H W) of a flow field (K, F - 1, H, W, 2): dense float32 on the device."""
+    require_device(flow)
+    if flow.dim() != 5 or flow.shape[4] != 2 or flow.dtype != torch.float32 or not flow.is_contiguous():
+        raise L.VsError(f"{what}: flow (K, F - 1, H, W, 2) dense float32")
+    K, Fp, H, W, _ = flow.shape
+    if Fp < 1 or not 1 <= H * W <= FLOW_MAX_PIXELS:
+        raise L.VsError(f"{what}: at least one flow frame of 1 <= H W <= 2^20 pixels")
+    return K, Fp, H * W
+
+
+def flow_median2(flow, absolute=False):
+    """(K, F - 1, 2) float32: np.median over (h, w) of each component of each frame of flow (K, F - 1, H, W, 2), of
+    the signed values or (absolute=True) of |flow|, bit for bit (vs_flow_median2).  A NaN in a component of a frame gives NaN for
+    that component."""
+    K, Fp, HW = _flow_dims(flow, "flow_median2")
+    out = torch.empty(K, Fp, 2, dtype=torch.float32, device=flow.device)
+    check(lib().vs_flow_median2(K * Fp, HW, flow.data_ptr(), int(bool(absolute)), out.data_ptr(), stream()),
+          "vs_flow_median2")
+    return out
+
+
+def flow_quantiles(flow, q=(10, 90), with_stats=False, workspace=None):
+    """(K, 2, 2) float32: [trial, component] -> (np.percentile(x, q[0]), np.percentile(x, q[1])) of
+    x = |flow[trial, ..., component]| as numpy 2 computes them for a float32 array and a scalar q (vs_flow_quantiles).
+    with_stats: also the (K, 2, 4) order statistics the two are interpolated between."""
+    K, Fp, HW = _flow_dims(flow, "flow_quantiles")
+    if K > 65535 or Fp * HW >= 1 << 31:
+        raise L.VsError("flow_quantiles: at most 65535 trials of fewer than 2^31 values per component")
+    if len(q) != 2 or not all(0 <= float(v) <= 100 for v in q):
+        raise L.VsError("flow_quantiles: q holds two percentiles in [0, 100]")
+    bounds = torch.empty(K, 2, 2, dtype=torch.float32, device=flow.device)
+    stats = torch.empty(K, 2, 4, dtype=torch.float32, device=flow.device) if with_stats else None
+    if K:
+        need = int(lib().vs_flow_quantiles_workspace_bytes(K))
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=flow.device)
+        elif workspace.device != flow.device or workspace.numel() * workspace.element_size() < need \
+                or not workspace.is_contiguous():
+            raise L.VsError(f"flow_quantiles: workspace of {need} bytes on the flow's device")
+        check(lib().vs_flow_quantiles(K, Fp, HW, flow.data_ptr(), float(q[0]), float(q[1]), bounds.data_ptr(),
+                                      ptr(stats), workspace.data_ptr(), stream()), "vs_flow_quantiles")
+    return (bounds, stats) if with_stats else bounds
+
+
+def flow_clip_mean(flow, bounds):
+    """(K, F - 1) float32: the mean over (h, w, 2) of clip(|flow|, bounds[k, c, 0], bounds[k, c, 1]) per frame, an
+    f64 sum rounded once (vs_flow_clip_mean).  bounds (K, 2, 2) float32 as flow_quantiles returns them."""
+    K, Fp, HW = _flow_dims(flow, "flow_clip_mean")
+    require_device(bounds)
+    if tuple(bounds.shape) != (K, 2, 2) or bounds.dtype != torch.float32 or not bounds.is_contiguous() \
+            or bounds.device != flow.device:
+        raise L.VsError("flow_clip_mean: bounds (K, 2, 2) dense float32 on the flow's device")
+    out = torch.empty(K, Fp, dtype=torch.float32, device=flow.device)
+    check(lib().vs_flow_clip_mean(K, Fp, HW, flow.data_ptr(), bounds.data_ptr(), out.data_ptr(), stream()),
+          "vs_flow_clip_mean")
+    return out
+
+
+def motion_energy(video):
+    """(K, F - 1) float32: the mean over the pixels of |video[k, f + 1] - video[k, f]| for video (K, F, H, W) uint8
+    or float32, read in place (vs_motion_energy).  uint8: integer differences, an exact sum."""
+    require_device(video)
+    if video.dim() != 4 or video.dtype not in (torch.uint8, torch.float32) or not video.is_contiguous():
+        raise L.VsError("motion_energy: video (K, F, H, W) dense uint8 / float32 (it is read in place; no copy is made)")
+    K, F, H, W = video.shape
+    if F < 2 or not 1 <= H * W <= FLOW_MAX_PIXELS:
+        raise L.VsError("motion_energy: at least two frames of 1 <= H W <= 2^20 pixels")
+    out = torch.empty(K, F - 1, dtype=torch.float32, device=video.device)
+    code = L.VS_U8 if video.dtype == torch.uint8 else L.VS_F32
+    check(lib().vs_motion_energy(code, K, F, H * W, video.data_ptr(), out.data_ptr(), stream()), "vs_motion_energy")
+    return out
