@@ -569,7 +569,8 @@ int vs_info_nce(int64_t n, int64_t m, int64_t E, const float* ref, const float* 
  * These are the ABI's first `const double*` arguments: every operand but y / gt is f64, and all arithmetic
  * and accumulation is f64.  1 <= C <= 32 and 1 <= r <= 8, else VS_EINVAL.  No atomics; reductions run in an
  * order fixed by the extents, so equal inputs give bitwise equal outputs.  Pointers 8-byte aligned, the
- * workspace 16-byte aligned.
+ * workspace 16-byte aligned.  This section's entries and the two below (wide inputs, pixels) share their MFMA
+ * products, scoring, reduction over bins and argument checks through csrc/rrr_core.h.
  * ------------------------------------------------------------------------------------------ */
 /* loss (device f64[1]) and, when dU / dV / db are given (all three, or all NULL = loss only: the reference's
    mses_val with l2 = 0), dU [N, C, r], dV [r, T], db [N, 1, T], WRITTEN.  y and X are read once; nothing of
@@ -912,7 +913,7 @@ int vs_g256_scratch_free(void);
 #define VS_KNOB_DW256_ALL   36   /* 1: the 768 x 768 projection dW on the 256 x 256 dW kernel too (default: split-K dW tiles) */
 #define VS_KNOB_LN_FWD_BLOCKS 37 /* LayerNorm forward (vectorised) grid cap (0 = default 768) */
 #define VS_KNOB_G256_A3     35   /* 256 x 256 forward / dX GEMM: the streamed A operand in three LDS slots (DMA two stages ahead, counted stage wait): 0 / 1 = on (default), 2 = off (two slots, round 5) */
-#define VS_KNOB_RRR_PIXEL_RECIP 38 /* vs_rrr_pixel_*: 1 = standardise with a reciprocal multiply instead of the division (last-bit differences; A/B only) */
+/* id 38 (rrr_pixel_recip, an A/B knob of vs_rrr_pixel_*) is retired since ABI v14: it reads 0 and setting it does nothing */
 #define VS_KNOB_COUNT       40
 int vs_knob_get(int knob);               /* VS_EINVAL for an unknown id */
 int vs_knob_set(int knob, int value);    /* returns the previous value; VS_EINVAL for an unknown id */

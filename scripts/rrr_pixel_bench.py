@@ -125,21 +125,6 @@ def main():
     us_p, us_lo, us_sc, us_st = (statistics.median(t) for t in (t_p, t_lo, t_sc, t_st))
     flops = 2 * 2.0 * K * T * (C + 1) * N
 
-    # A/B: the standardisation as a reciprocal multiply (knob rrr_pixel_recip) instead of the division
-    pixel()
-    ref = [t.clone() for t in (loss, dU, dV, db)]
-    L.knob_set("rrr_pixel_recip", 1)
-    try:
-        event_us(pixel, 1)
-        moved = [float((g - w).norm() / w.norm()) for g, w in zip((loss, dU, dV, db), ref)]
-        us_rp = statistics.median(event_us(pixel, a.calls) for _ in range(a.repeats))
-        us_rlo = statistics.median(event_us(loss_only, a.calls) for _ in range(a.repeats))
-    finally:
-        L.knob_set("rrr_pixel_recip", 0)
-    recip = {"loss_grad_us": round(us_rp, 1), "loss_only_us": round(us_rlo, 1),
-             "division_over_reciprocal": round(us_p / us_rp, 3),
-             "results_moved_by": dict(zip(("loss", "dU", "dV", "db"), moved))}
-
     # the whole fit from the pixels, with its peak memory (the video, y and the statistics are there already)
     def fit_pixel():
         return RRRGD(r, l2).fit({"s": (feats, y)}).func_evals
@@ -154,7 +139,6 @@ def main():
         "loss_grad_us": round(us_p, 1), "loss_grad_us_windows": [round(t, 1) for t in t_p],
         "loss_grad_f64_tflops": round(flops / us_p * 1e-6, 2),
         "loss_only_us": round(us_lo, 1), "loss_only_f64_tflops": round(0.5 * flops / us_lo * 1e-6, 2),
-        "reciprocal_standardisation_ab": recip,
         "score_us": round(us_sc, 1), "stats_us": round(us_st, 1),
         "stats_gbs": round(2.0 * X.numel() / us_st * 1e-3, 1),
         "fit_ms": round(ms_fit, 1), "fit_func_evals": int(evals), "fit_kernel_share": round(20 * us_p * 1e-3 / ms_fit, 3),

@@ -15,35 +15,24 @@
 //                          order).  When T * ceil(N/64) is a small grid the trials are also split over S blocks
 //                          (ordered partials).  Writes part[s][t][c][n] (rows 0..C = G, row C+1 = sq):
 //                          S T (C+2) N doubles, nothing of size K T N.  y and X are read exactly once.
-//   2. rrr_reduce_t_kernel block = 64 neurons x 4 waves, one row c.  Sums the S partials, forms
-//                          H = G + 2 l2 beta (kept [t][c][n] for step 3), db = H[:,C,:], and over its slice of the
-//                          bins dU[n,c,:] += H V[:,t] and the loss terms; waves combine through LDS in wave order.
+//   2. rrr_reduce_t_kernel (rrr_core.h, loss terms per lane) sums the S partials and forms H = G + 2 l2 beta
+//                          over partial 0 (kept [t][c][n], C+2 rows per bin, for step 3), db, dU and the loss terms.
 //   3. rrr_dv_kernel       block = one bin t: dV[:,t] = sum_{n,c} U[n,c,:] H[t][c][n] (strided + LDS tree).
 //   4. rrr_loss_kernel     one block: loss = sum of the (C+2) N loss terms (strided + LDS tree).
-// vs_rrr_score: rrr_score_kernel (block = 64 neurons x 4 waves, wave = a slice of the held-out trials; a thread
-//   walks its neuron's T bins of one trial, so the trial's R^2 is complete in registers) + rrr_score_final_kernel.
-#include <math.h>
+// Scoring, for all three units: rrr_score_kernel (block = 64 neurons x 4 waves, wave = a slice of the held-out
+//   trials; a thread walks its neuron's T bins of one trial, so the trial's R^2 is complete in registers), over
+//   where yhat comes from (computed here from X, U, V, b: vs_rrr_score; read from the workspace: the wide and
+//   pixel entries through rrr_score_yhat) + rrr_score_final_kernel.
+// This unit also holds the kernels of rrr_core.h that are not templates (rrr_loss_kernel, rrr_dv_sum_kernel) and
+// the argument checks the three units' entries share.
+#include <stdio.h>
 
-#include "common.h"
+#include "rrr_core.h"
 
 namespace vs {
 
 constexpr int kRrrMaxC = 32;
-constexpr int kRrrMaxR = 8;
-constexpr int kRrrWaves = 4;
 constexpr int kRrrMaxSplit = 16;
-
-template <typename YT> __device__ __forceinline__ double ld_f64(const YT* p) { return (double)*p; }
-__device__ __forceinline__ int64_t dcdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// beta[n,c,t] for c < C (u = U[n,c,:] in registers)
-__device__ __forceinline__ double rrr_beta(const double* u, const double* __restrict__ V, int r, int64_t T, int64_t t) {
-  double s = 0.0;
-#pragma unroll
-  for (int j = 0; j < kRrrMaxR; ++j)
-    if (j < r) s = fma(u[j], V[(int64_t)j * T + t], s);
-  return s;
-}
 
 // CP: C + 1 rounded up to a compiled size (rows C+1 .. CP-1 are zeros)
 template <typename YT, int CP, bool GRAD>
@@ -124,97 +113,12 @@ __global__ __launch_bounds__(256) void rrr_accum_kernel(int64_t K, int64_t T, in
   }
 }
 
-// grid (ceil(N/64), C+2): row c <= C of H / dU / db and its l2 term, row C+1 the squared residuals.
-// grad == 0 (loss only): rows 0..C have no partials and only their l2 terms are formed.
-__global__ __launch_bounds__(256) void rrr_reduce_t_kernel(int64_t T, int64_t N, int C, int r, int S, double l2, int grad,
-                                                           const double* __restrict__ part,
-                                                           const double* __restrict__ U, const double* __restrict__ V,
-                                                           const double* __restrict__ b, double* __restrict__ H,
-                                                           double* __restrict__ dU, double* __restrict__ db,
-                                                           double* __restrict__ lossp) {
-  __shared__ double red[(kRrrWaves - 1) * (kRrrMaxR + 1) * 64];
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int c = blockIdx.y;
-  const int64_t n = (int64_t)blockIdx.x * 64 + lane;
-  const bool live = n < N;
-  const int C1 = C + 1;
-  const int64_t tper = dcdiv(T, kRrrWaves);
-  const int64_t t0 = (int64_t)w * tper;
-  const int64_t t1 = t0 + tper < T ? t0 + tper : T;
-  double u[kRrrMaxR], du[kRrrMaxR];
-#pragma unroll
-  for (int j = 0; j < kRrrMaxR; ++j) {
-    u[j] = (live && c < C && j < r) ? U[(n * C + c) * r + j] : 0.0;
-    du[j] = 0.0;
-  }
-  double term = 0.0;  // sum beta^2 (rows 0..C) or sum res^2 (row C+1)
-  if (live) {
-    for (int64_t t = t0; t < t1; ++t) {
-      double g = 0.0;
-      if (grad || c == C1)
-        for (int s = 0; s < S; ++s) g += part[(((int64_t)s * T + t) * (C + 2) + c) * N + n];
-      if (c == C1) {
-        term += g;
-        continue;
-      }
-      const double be = c < C ? rrr_beta(u, V, r, T, t) : b[n * T + t];
-      term = fma(be, be, term);
-      if (grad) {
-        const double h = fma(2.0 * l2, be, g);
-        H[(t * C1 + c) * N + n] = h;
-        if (c == C) {
-          db[n * T + t] = h;
-        } else {
-#pragma unroll
-          for (int j = 0; j < kRrrMaxR; ++j)
-            if (j < r) du[j] = fma(h, V[(int64_t)j * T + t], du[j]);
-        }
-      }
-    }
-  }
-  if (w > 0) {
-    double* p = red + (size_t)(w - 1) * (kRrrMaxR + 1) * 64 + lane;
-    p[0] = term;
-#pragma unroll
-    for (int j = 0; j < kRrrMaxR; ++j) p[(j + 1) * 64] = du[j];
-  }
-  __syncthreads();
-  if (w == 0 && live) {
-    for (int v = 1; v < kRrrWaves; ++v) {
-      const double* p = red + (size_t)(v - 1) * (kRrrMaxR + 1) * 64 + lane;
-      term += p[0];
-#pragma unroll
-      for (int j = 0; j < kRrrMaxR; ++j) du[j] += p[(j + 1) * 64];
-    }
-    lossp[(int64_t)c * N + n] = c == C1 ? term : l2 * term;
-    if (grad && c < C) {
-#pragma unroll
-      for (int j = 0; j < kRrrMaxR; ++j)
-        if (j < r) dU[(n * C + c) * r + j] = du[j];
-    }
-  }
-}
-
-// fixed-shape block reduction (256 threads); every thread gets the sum
-__device__ double rrr_block_sum(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const double out = red[0];
-  __syncthreads();
-  return out;
-}
-
-// block t: dV[j,t] = sum over i = c N + n (c < C) of U[n,c,j] H[t][c][n]
+// block t: dV[j,t] = sum over i = c N + n (c < C) of U[n,c,j] H[t][c][n] (H: C+2 rows per bin)
 __global__ __launch_bounds__(256) void rrr_dv_kernel(int64_t T, int64_t N, int C, int r, const double* __restrict__ U,
                                                      const double* __restrict__ H, double* __restrict__ dV) {
   __shared__ double red[256];
   const int64_t t = blockIdx.x;
-  const double* h = H + t * (C + 1) * N;
+  const double* h = H + t * (C + 2) * N;
   double acc[kRrrMaxR];
 #pragma unroll
   for (int j = 0; j < kRrrMaxR; ++j) acc[j] = 0.0;
@@ -241,10 +145,29 @@ __global__ __launch_bounds__(256) void rrr_loss_kernel(int64_t count, const doub
   if (threadIdx.x == 0) loss[0] = a;
 }
 
+void rrr_launch_loss(hipStream_t s, int64_t count, const double* lossp, double* loss) {
+  hipLaunchKernelGGL(rrr_loss_kernel, dim3(1), dim3(256), 0, s, count, lossp, loss);
+}
+
+// grid ceil(r T / 256): dV[i] = sum of element i's partials, ascending
+__global__ __launch_bounds__(256) void rrr_dv_sum_kernel(int64_t rT, int64_t count, int64_t stride,
+                                                         const double* __restrict__ dVp, double* __restrict__ dV) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rT) return;
+  double s = 0.0;
+  for (int64_t p = 0; p < count; ++p) s += dVp[p * stride + i];
+  dV[i] = s;
+}
+
+void rrr_launch_dv_sum(hipStream_t s, int64_t T, int r, int64_t count, int64_t stride, const double* dVp, double* dV) {
+  hipLaunchKernelGGL(rrr_dv_sum_kernel, dim3((unsigned)cdiv(r * T, 256)), dim3(256), 0, s, r * T, count, stride, dVp,
+                     dV);
+}
+
 struct RrrWs {
   int S;
   int64_t kper;
-  size_t part, H, lossp, total;  // byte offsets
+  size_t part, lossp, total;  // byte offsets (H overwrites partial 0 of part)
 };
 static RrrWs rrr_ws(int64_t K, int64_t T, int64_t N, int64_t C) {
   RrrWs w;
@@ -259,9 +182,9 @@ static RrrWs rrr_ws(int64_t K, int64_t T, int64_t N, int64_t C) {
   auto al = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
   size_t off = 0;
   w.part = off;  off += al((size_t)w.S * T * (C + 2) * N * 8);
-  w.H = off;     off += al((size_t)T * (C + 1) * N * 8);
   w.lossp = off; off += al((size_t)(C + 2) * N * 8);
-  w.total = off;
+  // unused: the size callers were told before H moved into partial 0 (T (C+1) N doubles more) is kept
+  w.total = off + al((size_t)T * (C + 1) * N * 8);
   return w;
 }
 
@@ -295,11 +218,29 @@ static void rrr_dispatch_accum(int C1, bool grad, dim3 grid, hipStream_t s, int6
 constexpr int kScoreStats = 5;
 constexpr int kScoreMaxChunks = 256;
 
+// where yhat[k,t,n] comes from: the narrow entry's operands (X[k,t,:] is wave-uniform) ...
+struct RrrYhatComputed {
+  const double *X, *U, *V, *b;
+  int C, r;
+  __device__ __forceinline__ double operator()(int64_t k, int64_t t, int64_t n, int64_t T, int64_t N) const {
+    const double* xr = X + (k * T + t) * (C + 1);
+    const double* un = U + n * C * r;
+    double yh = 0.0;
+    for (int c = 0; c < C; ++c) yh = fma(xr[c], rrr_beta(un + c * r, V, r, T, t), yh);
+    return fma(xr[C], b[n * T + t], yh);
+  }
+};
+// ... or the [K][T][N] a forward product left in the workspace
+struct RrrYhatStored {
+  const double* yhat;
+  __device__ __forceinline__ double operator()(int64_t k, int64_t t, int64_t n, int64_t T, int64_t N) const {
+    return yhat[(k * T + t) * N + n];
+  }
+};
+
 // grid (ceil(N/64), chunks of the trials); wave w of a block takes a slice of the chunk.  stat [chunk][5][N].
-template <typename YT>
-__global__ __launch_bounds__(256) void rrr_score_kernel(int64_t K, int64_t T, int64_t N, int C, int r, int64_t kchunk,
-                                                        const double* __restrict__ X, const double* __restrict__ U,
-                                                        const double* __restrict__ V, const double* __restrict__ b,
+template <typename YT, typename Yhat>
+__global__ __launch_bounds__(256) void rrr_score_kernel(int64_t K, int64_t T, int64_t N, int64_t kchunk, const Yhat yhat,
                                                         const double* __restrict__ mean_y,
                                                         const double* __restrict__ std_y, const YT* __restrict__ gt,
                                                         double* __restrict__ pred, double* __restrict__ stat) {
@@ -308,24 +249,18 @@ __global__ __launch_bounds__(256) void rrr_score_kernel(int64_t K, int64_t T, in
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t n = (int64_t)blockIdx.x * 64 + lane;
   const bool live = n < N;
-  const int C1 = C + 1;
   const int64_t kw = dcdiv(kchunk, kRrrWaves);
   const int64_t kend = ((int64_t)blockIdx.y + 1) * kchunk < K ? ((int64_t)blockIdx.y + 1) * kchunk : K;
   const int64_t k0 = (int64_t)blockIdx.y * kchunk + (int64_t)w * kw;
   const int64_t k1 = k0 + kw < kend ? k0 + kw : kend;
   double st[kScoreStats] = {0, 0, 0, 0, 0};
   if (live) {
-    const double* un = U + n * C * r;
     for (int64_t k = k0; k < k1; ++k) {
       double sy = 0.0, res = 0.0;
       for (int64_t t = 0; t < T; ++t) {
-        const double* xr = X + (k * T + t) * C1;
-        double yh = 0.0;
-        for (int c = 0; c < C; ++c) yh = fma(xr[c], rrr_beta(un + c * r, V, r, T, t), yh);
-        yh = fma(xr[C], b[n * T + t], yh);
-        double p = fma(yh, std_y[t * N + n], mean_y[t * N + n]);
-        p = p < 1e-3 ? 1e-3 : p;   // np.clip(pred, 1e-3, None): a NaN stays a NaN
         const int64_t at = (k * T + t) * N + n;
+        double p = fma(yhat(k, t, n, T, N), std_y[t * N + n], mean_y[t * N + n]);
+        p = p < 1e-3 ? 1e-3 : p;   // np.clip(pred, 1e-3, None): a NaN stays a NaN
         if (pred) pred[at] = p;
         const double g = ld_f64(gt + at);
         st[0] += g;
@@ -414,16 +349,70 @@ __global__ __launch_bounds__(256) void rrr_score_final_kernel(int64_t K, int64_t
 struct ScoreWs {
   int chunks;
   int64_t kchunk;
-  size_t total;
+  size_t stat, total;   // byte offsets; the yhat piece, when present, is at 0
 };
-static ScoreWs score_ws(int64_t K, int64_t N) {
+static ScoreWs score_ws(int64_t K, int64_t T, int64_t N, bool yhat) {
   ScoreWs w;
   int64_t ch = cdiv(K, kRrrWaves);
   if (ch > kScoreMaxChunks) ch = kScoreMaxChunks;
   w.kchunk = cdiv(K, ch);
   w.chunks = (int)cdiv(K, w.kchunk);
-  w.total = ((size_t)w.chunks * kScoreStats * N * 8 + 255) / 256 * 256;
+  auto al = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+  w.stat = yhat ? al((size_t)K * T * N * 8) : 0;
+  w.total = w.stat + al((size_t)w.chunks * kScoreStats * N * 8);
   return w;
+}
+
+size_t rrr_score_workspace_bytes(int64_t K, int64_t T, int64_t N, bool yhat) { return score_ws(K, T, N, yhat).total; }
+
+template <typename Yhat>
+static int rrr_score_run(hipStream_t s, int64_t K, int64_t T, int64_t N, const ScoreWs& w, const Yhat& yhat,
+                         const double* mean_y, const double* std_y, const void* gt, int32_t gt_dtype, double* pred,
+                         double* bps, double* r2, double* out, void* workspace) {
+  double* stat = (double*)((char*)workspace + w.stat);
+  const dim3 grid((unsigned)cdiv(N, 64), (unsigned)w.chunks);
+  if (gt_dtype == VS_F32)
+    hipLaunchKernelGGL((rrr_score_kernel<float, Yhat>), grid, dim3(256), 0, s, K, T, N, w.kchunk, yhat, mean_y, std_y,
+                       (const float*)gt, pred, stat);
+  else
+    hipLaunchKernelGGL((rrr_score_kernel<double, Yhat>), grid, dim3(256), 0, s, K, T, N, w.kchunk, yhat, mean_y, std_y,
+                       (const double*)gt, pred, stat);
+  VS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rrr_score_final_kernel, dim3(1), dim3(256), 0, s, K, T, N, w.chunks, (const double*)stat, bps, r2,
+                     out);
+  VS_LAUNCH_CHECK();
+  return VS_OK;
+}
+
+int rrr_score_yhat(hipStream_t s, int64_t K, int64_t T, int64_t N, const double* mean_y, const double* std_y,
+                   const void* gt, int32_t gt_dtype, double* pred, double* bps, double* r2, double* out,
+                   void* workspace) {
+  return rrr_score_run(s, K, T, N, score_ws(K, T, N, true), RrrYhatStored{(const double*)workspace}, mean_y, std_y, gt,
+                       gt_dtype, pred, bps, r2, out, workspace);
+}
+
+// ---- argument checks --------------------------------------------------------------------------------------
+static int rrr_fail(const char* entry, const char* what) {
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: %s", entry, what);
+  set_error(msg);
+  return VS_EINVAL;
+}
+
+int rrr_check_loss_grad(const char* entry, int32_t y_dtype, bool ptrs, const double* dU, const double* dV,
+                        const double* db, const void* workspace) {
+  if (y_dtype != VS_F32 && y_dtype != VS_F64) return rrr_fail(entry, "y must be f32 or f64");
+  if (!ptrs) return rrr_fail(entry, "null pointer");
+  if ((dU || dV || db) && !(dU && dV && db)) return rrr_fail(entry, "dU, dV, db are given together or not at all");
+  if (!aligned16(workspace)) return rrr_fail(entry, "workspace must be 16-byte aligned");
+  return VS_OK;
+}
+
+int rrr_check_score(const char* entry, int32_t gt_dtype, bool ptrs, const void* workspace) {
+  if (gt_dtype != VS_F32 && gt_dtype != VS_F64) return rrr_fail(entry, "gt must be f32 or f64");
+  if (!ptrs) return rrr_fail(entry, "null pointer");
+  if (!aligned16(workspace)) return rrr_fail(entry, "workspace must be 16-byte aligned");
+  return VS_OK;
 }
 
 static bool rrr_dims_ok(int64_t K, int64_t T, int64_t N, int64_t C, int64_t r) {
@@ -446,16 +435,13 @@ extern "C" int vs_rrr_loss_grad(int64_t K, int64_t T, int64_t N, int64_t C, int6
   VS_REQUIRE(C >= 1 && C <= kRrrMaxC, "vs_rrr_loss_grad: 1 <= C <= 32 features (without the bias column)");
   VS_REQUIRE(r >= 1 && r <= kRrrMaxR, "vs_rrr_loss_grad: 1 <= r <= 8 components");
   VS_REQUIRE(rrr_dims_ok(K, T, N, C, r), "vs_rrr_loss_grad: K, T, N must be positive (T <= 65535)");
-  VS_REQUIRE(y_dtype == VS_F32 || y_dtype == VS_F64, "vs_rrr_loss_grad: y must be f32 or f64");
-  VS_REQUIRE(X && y && U && V && b && loss && workspace, "vs_rrr_loss_grad: null pointer");
-  const bool grad = dU || dV || db;
-  VS_REQUIRE(!grad || (dU && dV && db), "vs_rrr_loss_grad: dU, dV, db are given together or not at all");
-  VS_REQUIRE((((uintptr_t)workspace) & 15u) == 0, "vs_rrr_loss_grad: workspace must be 16-byte aligned");
+  VS_CALL(rrr_check_loss_grad("vs_rrr_loss_grad", y_dtype, X && y && U && V && b && loss && workspace, dU, dV, db,
+                              workspace));
+  const bool grad = dU != nullptr;
   hipStream_t s = (hipStream_t)stream;
   const RrrWs w = rrr_ws(K, T, N, C);
   char* ws = (char*)workspace;
   double* part = (double*)(ws + w.part);
-  double* H = (double*)(ws + w.H);
   double* lossp = (double*)(ws + w.lossp);
   ScopedTimer timer(VS_TIMER_MISC, s,
                     (double)K * T * ((double)N * (y_dtype == VS_F32 ? 4.0 : 8.0) + (C + 1) * 8.0));
@@ -465,21 +451,22 @@ extern "C" int vs_rrr_loss_grad(int64_t K, int64_t T, int64_t N, int64_t C, int6
   else
     rrr_dispatch_accum<double>((int)C + 1, grad, grid, s, K, T, N, (int)C, (int)r, w.kper, X, y, U, V, b, part);
   VS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rrr_reduce_t_kernel, dim3((unsigned)cdiv(N, 64), (unsigned)(C + 2)), dim3(256), 0, s, T, N, (int)C,
-                     (int)r, w.S, l2, grad ? 1 : 0, (const double*)part, U, V, b, H, dU, db, lossp);
+  hipLaunchKernelGGL(rrr_reduce_t_kernel<false>, dim3((unsigned)cdiv(N, 64), (unsigned)(C + 2)), dim3(256), 0, s, T, N,
+                     (int)C, (int)r, w.S, l2, grad ? 1 : 0, part, U, V, b, dU, db, lossp);
   VS_LAUNCH_CHECK();
   if (grad) {
-    hipLaunchKernelGGL(rrr_dv_kernel, dim3((unsigned)T), dim3(256), 0, s, T, N, (int)C, (int)r, U, (const double*)H, dV);
+    hipLaunchKernelGGL(rrr_dv_kernel, dim3((unsigned)T), dim3(256), 0, s, T, N, (int)C, (int)r, U, (const double*)part,
+                       dV);
     VS_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(rrr_loss_kernel, dim3(1), dim3(256), 0, s, (int64_t)(C + 2) * N, (const double*)lossp, loss);
+  rrr_launch_loss(s, (int64_t)(C + 2) * N, lossp, loss);
   VS_LAUNCH_CHECK();
   return VS_OK;
 }
 
 extern "C" size_t vs_rrr_score_workspace_bytes(int64_t K, int64_t N) {
   if (K <= 0 || N <= 0) return 0;
-  return score_ws(K, N).total;
+  return rrr_score_workspace_bytes(K, 1, N, false);
 }
 
 extern "C" int vs_rrr_score(int64_t K, int64_t T, int64_t N, int64_t C, int64_t r, const double* X, const double* U,
@@ -489,25 +476,11 @@ extern "C" int vs_rrr_score(int64_t K, int64_t T, int64_t N, int64_t C, int64_t 
   VS_REQUIRE(C >= 1 && C <= kRrrMaxC, "vs_rrr_score: 1 <= C <= 32 features (without the bias column)");
   VS_REQUIRE(r >= 1 && r <= kRrrMaxR, "vs_rrr_score: 1 <= r <= 8 components");
   VS_REQUIRE(rrr_dims_ok(K, T, N, C, r), "vs_rrr_score: K, T, N must be positive (T <= 65535)");
-  VS_REQUIRE(gt_dtype == VS_F32 || gt_dtype == VS_F64, "vs_rrr_score: gt must be f32 or f64");
-  VS_REQUIRE(X && U && V && b && mean_y && std_y && gt && bps && r2 && out && workspace,
-             "vs_rrr_score: null pointer");
-  VS_REQUIRE((((uintptr_t)workspace) & 15u) == 0, "vs_rrr_score: workspace must be 16-byte aligned");
+  VS_CALL(rrr_check_score("vs_rrr_score", gt_dtype,
+                          X && U && V && b && mean_y && std_y && gt && bps && r2 && out && workspace, workspace));
   hipStream_t s = (hipStream_t)stream;
-  const ScoreWs w = score_ws(K, N);
-  double* stat = (double*)workspace;
   ScopedTimer timer(VS_TIMER_MISC, s,
                     (double)K * T * ((double)N * ((gt_dtype == VS_F32 ? 4.0 : 8.0) + (pred ? 8.0 : 0.0)) + (C + 1) * 8.0));
-  const dim3 grid((unsigned)cdiv(N, 64), (unsigned)w.chunks);
-  if (gt_dtype == VS_F32)
-    hipLaunchKernelGGL(rrr_score_kernel<float>, grid, dim3(256), 0, s, K, T, N, (int)C, (int)r, w.kchunk, X, U, V, b,
-                       mean_y, std_y, (const float*)gt, pred, stat);
-  else
-    hipLaunchKernelGGL(rrr_score_kernel<double>, grid, dim3(256), 0, s, K, T, N, (int)C, (int)r, w.kchunk, X, U, V, b,
-                       mean_y, std_y, (const double*)gt, pred, stat);
-  VS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rrr_score_final_kernel, dim3(1), dim3(256), 0, s, K, T, N, w.chunks, (const double*)stat, bps, r2,
-                     out);
-  VS_LAUNCH_CHECK();
-  return VS_OK;
+  return rrr_score_run(s, K, T, N, score_ws(K, T, N, false), RrrYhatComputed{X, U, V, b, (int)C, (int)r}, mean_y, std_y,
+                       gt, gt_dtype, pred, bps, r2, out, workspace);
 }

@@ -448,6 +448,33 @@ def _f64_code(t):
     return L.VS_F64 if t.dtype == torch.float64 else L.VS_F32
 
 
+def _rrr_grad_outputs(what, U, V, b, loss, dU, dV, db):
+    """The output checks of the three *_loss_grad entries."""
+    for g, ref in ((dU, U), (dV, V), (db, b)):
+        if g is not None and (g.numel() != ref.numel() or g.dtype != torch.float64 or not g.is_contiguous()):
+            raise L.VsError(f"{what}: dU / dV / db are dense float64 of the shapes of U / V / b")
+    if loss.dtype != torch.float64 or loss.numel() < 1:
+        raise L.VsError(f"{what}: loss must hold one float64")
+
+
+def _rrr_score_outputs(what, K, T, N, mean_y, std_y, bps, r2, out, pred):
+    """The checks of the three *_score entries on the statistics of y and the outputs."""
+    for t, numel in ((mean_y, T * N), (std_y, T * N), (bps, N), (r2, N), (pred, K * T * N)):
+        if t is not None and (t.numel() != numel or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise L.VsError(f"{what}: mean_y / std_y [T, N], bps / r2 [N], pred [K, T, N] dense float64")
+    if out.dtype != torch.float64 or out.numel() < 2:
+        raise L.VsError(f"{what}: out must hold two float64")
+
+
+def _rrr_workspace(what, need, workspace, device):
+    """A workspace of `need` bytes: a new one, or the caller's after checking its size."""
+    if workspace is None:
+        return torch.empty(need // 8 + 2, dtype=torch.float64, device=device)
+    if workspace.numel() * workspace.element_size() < need:
+        raise L.VsError(f"{what}: workspace too small")
+    return workspace
+
+
 def rrr_loss_grad_workspace_bytes(K, T, N, C):
     return int(lib().vs_rrr_loss_grad_workspace_bytes(K, T, N, C))
 
@@ -457,16 +484,8 @@ def rrr_loss_grad(X, y, U, V, b, l2, loss, dU=None, dV=None, db=None, workspace=
     (together), its gradients (vs_rrr_loss_grad).  1 <= C <= 32, 1 <= r <= 8."""
     require_device(X, y, U, V, b, loss, dU, dV, db, workspace)
     K, T, N, C, r = _rrr_dims(X, y, U, V, b, "rrr_loss_grad")
-    for g, ref in ((dU, U), (dV, V), (db, b)):
-        if g is not None and (g.numel() != ref.numel() or g.dtype != torch.float64 or not g.is_contiguous()):
-            raise L.VsError("rrr_loss_grad: dU / dV / db are dense float64 of the shapes of U / V / b")
-    if loss.dtype != torch.float64 or loss.numel() < 1:
-        raise L.VsError("rrr_loss_grad: loss must hold one float64")
-    need = rrr_loss_grad_workspace_bytes(K, T, N, C) if 1 <= C <= 32 else 0
-    if workspace is None:
-        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise L.VsError("rrr_loss_grad: workspace too small")
+    _rrr_grad_outputs("rrr_loss_grad", U, V, b, loss, dU, dV, db)
+    workspace = _rrr_workspace("rrr_loss_grad", rrr_loss_grad_workspace_bytes(K, T, N, C), workspace, X.device)
     check(lib().vs_rrr_loss_grad(K, T, N, C, r, X.data_ptr(), y.data_ptr(), _f64_code(y), U.data_ptr(), V.data_ptr(),
                                  b.data_ptr(), float(l2), loss.data_ptr(), ptr(dU), ptr(dV), ptr(db),
                                  workspace.data_ptr(), stream()), "vs_rrr_loss_grad")
@@ -483,16 +502,8 @@ def rrr_score(X, U, V, b, mean_y, std_y, gt, bps, r2, out, pred=None, workspace=
     [N], and out f64[2] = their NaN-ignoring means over neurons (co_bps, mean R^2)."""
     require_device(X, U, V, b, mean_y, std_y, gt, bps, r2, out, pred, workspace)
     K, T, N, C, r = _rrr_dims(X, gt, U, V, b, "rrr_score")
-    for t, numel in ((mean_y, T * N), (std_y, T * N), (bps, N), (r2, N), (pred, K * T * N)):
-        if t is not None and (t.numel() != numel or t.dtype != torch.float64 or not t.is_contiguous()):
-            raise L.VsError("rrr_score: mean_y / std_y [T, N], bps / r2 [N], pred [K, T, N] dense float64")
-    if out.dtype != torch.float64 or out.numel() < 2:
-        raise L.VsError("rrr_score: out must hold two float64")
-    need = rrr_score_workspace_bytes(K, N)
-    if workspace is None:
-        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise L.VsError("rrr_score: workspace too small")
+    _rrr_score_outputs("rrr_score", K, T, N, mean_y, std_y, bps, r2, out, pred)
+    workspace = _rrr_workspace("rrr_score", rrr_score_workspace_bytes(K, N), workspace, X.device)
     check(lib().vs_rrr_score(K, T, N, C, r, X.data_ptr(), U.data_ptr(), V.data_ptr(), b.data_ptr(), mean_y.data_ptr(),
                              std_y.data_ptr(), gt.data_ptr(), _f64_code(gt), ptr(pred), bps.data_ptr(), r2.data_ptr(),
                              out.data_ptr(), workspace.data_ptr(), stream()), "vs_rrr_score")
@@ -508,16 +519,9 @@ def rrr_wide_loss_grad(X, y, U, V, b, l2, loss, dU=None, dV=None, db=None, works
     float64 MFMA).  The same operands, results and checks; 1 <= r <= 8."""
     require_device(X, y, U, V, b, loss, dU, dV, db, workspace)
     K, T, N, C, r = _rrr_dims(X, y, U, V, b, "rrr_wide_loss_grad")
-    for g, ref in ((dU, U), (dV, V), (db, b)):
-        if g is not None and (g.numel() != ref.numel() or g.dtype != torch.float64 or not g.is_contiguous()):
-            raise L.VsError("rrr_wide_loss_grad: dU / dV / db are dense float64 of the shapes of U / V / b")
-    if loss.dtype != torch.float64 or loss.numel() < 1:
-        raise L.VsError("rrr_wide_loss_grad: loss must hold one float64")
-    need = rrr_wide_loss_grad_workspace_bytes(K, T, N, C) if 1 <= C <= 1024 else 0
-    if workspace is None:
-        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise L.VsError("rrr_wide_loss_grad: workspace too small")
+    _rrr_grad_outputs("rrr_wide_loss_grad", U, V, b, loss, dU, dV, db)
+    workspace = _rrr_workspace("rrr_wide_loss_grad", rrr_wide_loss_grad_workspace_bytes(K, T, N, C), workspace,
+                               X.device)
     check(lib().vs_rrr_wide_loss_grad(K, T, N, C, r, X.data_ptr(), y.data_ptr(), _f64_code(y), U.data_ptr(),
                                       V.data_ptr(), b.data_ptr(), float(l2), loss.data_ptr(), ptr(dU), ptr(dV),
                                       ptr(db), workspace.data_ptr(), stream()), "vs_rrr_wide_loss_grad")
@@ -532,16 +536,8 @@ def rrr_wide_score(X, U, V, b, mean_y, std_y, gt, bps, r2, out, pred=None, works
     """rrr_score for 1 <= C <= 1024 features (vs_rrr_wide_score): the same operands, results and checks."""
     require_device(X, U, V, b, mean_y, std_y, gt, bps, r2, out, pred, workspace)
     K, T, N, C, r = _rrr_dims(X, gt, U, V, b, "rrr_wide_score")
-    for t, numel in ((mean_y, T * N), (std_y, T * N), (bps, N), (r2, N), (pred, K * T * N)):
-        if t is not None and (t.numel() != numel or t.dtype != torch.float64 or not t.is_contiguous()):
-            raise L.VsError("rrr_wide_score: mean_y / std_y [T, N], bps / r2 [N], pred [K, T, N] dense float64")
-    if out.dtype != torch.float64 or out.numel() < 2:
-        raise L.VsError("rrr_wide_score: out must hold two float64")
-    need = rrr_wide_score_workspace_bytes(K, T, N)
-    if workspace is None:
-        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise L.VsError("rrr_wide_score: workspace too small")
+    _rrr_score_outputs("rrr_wide_score", K, T, N, mean_y, std_y, bps, r2, out, pred)
+    workspace = _rrr_workspace("rrr_wide_score", rrr_wide_score_workspace_bytes(K, T, N), workspace, X.device)
     check(lib().vs_rrr_wide_score(K, T, N, C, r, X.data_ptr(), U.data_ptr(), V.data_ptr(), b.data_ptr(),
                                   mean_y.data_ptr(), std_y.data_ptr(), gt.data_ptr(), _f64_code(gt), ptr(pred),
                                   bps.data_ptr(), r2.data_ptr(), out.data_ptr(), workspace.data_ptr(), stream()),
@@ -612,16 +608,9 @@ def rrr_pixel_loss_grad(X, idx, mean, std, y, U, V, b, l2, loss, dU=None, dV=Non
     0 <= idx < F (PixelFeatures checks it once); the kernel clamps."""
     require_device(X, idx, mean, std, y, U, V, b, loss, dU, dV, db, workspace)
     K, F, T, N, C, r, code = _rrr_pixel_dims(X, idx, mean, std, y, U, V, b, "rrr_pixel_loss_grad")
-    for g, ref in ((dU, U), (dV, V), (db, b)):
-        if g is not None and (g.numel() != ref.numel() or g.dtype != torch.float64 or not g.is_contiguous()):
-            raise L.VsError("rrr_pixel_loss_grad: dU / dV / db are dense float64 of the shapes of U / V / b")
-    if loss.dtype != torch.float64 or loss.numel() < 1:
-        raise L.VsError("rrr_pixel_loss_grad: loss must hold one float64")
-    need = rrr_pixel_loss_grad_workspace_bytes(K, T, N, C, r)
-    if workspace is None:
-        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise L.VsError("rrr_pixel_loss_grad: workspace too small")
+    _rrr_grad_outputs("rrr_pixel_loss_grad", U, V, b, loss, dU, dV, db)
+    workspace = _rrr_workspace("rrr_pixel_loss_grad", rrr_pixel_loss_grad_workspace_bytes(K, T, N, C, r), workspace,
+                               X.device)
     check(lib().vs_rrr_pixel_loss_grad(K, F, T, N, C, r, X.data_ptr(), code, idx.data_ptr(), mean.data_ptr(),
                                        std.data_ptr(), y.data_ptr(), _f64_code(y), U.data_ptr(), V.data_ptr(),
                                        b.data_ptr(), float(l2), loss.data_ptr(), ptr(dU), ptr(dV), ptr(db),
@@ -638,16 +627,8 @@ def rrr_pixel_score(X, idx, mean, std, U, V, b, mean_y, std_y, gt, bps, r2, out,
     and checks of rrr_wide_score."""
     require_device(X, idx, mean, std, U, V, b, mean_y, std_y, gt, bps, r2, out, pred, workspace)
     K, F, T, N, C, r, code = _rrr_pixel_dims(X, idx, mean, std, gt, U, V, b, "rrr_pixel_score")
-    for t, numel in ((mean_y, T * N), (std_y, T * N), (bps, N), (r2, N), (pred, K * T * N)):
-        if t is not None and (t.numel() != numel or t.dtype != torch.float64 or not t.is_contiguous()):
-            raise L.VsError("rrr_pixel_score: mean_y / std_y [T, N], bps / r2 [N], pred [K, T, N] dense float64")
-    if out.dtype != torch.float64 or out.numel() < 2:
-        raise L.VsError("rrr_pixel_score: out must hold two float64")
-    need = rrr_pixel_score_workspace_bytes(K, T, N)
-    if workspace is None:
-        workspace = torch.empty(need // 8 + 2, dtype=torch.float64, device=X.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise L.VsError("rrr_pixel_score: workspace too small")
+    _rrr_score_outputs("rrr_pixel_score", K, T, N, mean_y, std_y, bps, r2, out, pred)
+    workspace = _rrr_workspace("rrr_pixel_score", rrr_pixel_score_workspace_bytes(K, T, N), workspace, X.device)
     check(lib().vs_rrr_pixel_score(K, F, T, N, C, r, X.data_ptr(), code, idx.data_ptr(), mean.data_ptr(),
                                    std.data_ptr(), U.data_ptr(), V.data_ptr(), b.data_ptr(), mean_y.data_ptr(),
                                    std_y.data_ptr(), gt.data_ptr(), _f64_code(gt), ptr(pred), bps.data_ptr(),

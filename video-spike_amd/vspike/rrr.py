@@ -23,6 +23,8 @@ a view of the video in its own dtype with the training statistics; such sessions
 """
 from __future__ import annotations
 
+from functools import partial
+
 import numpy as np
 import torch
 
@@ -50,31 +52,26 @@ def init_params(T: int, N: int, C: int, r: int):
 
 
 class RRR:
-    """One session's RRRGD.  `fit(X, y)` takes standardised device tensors: X [K, T, C+1] float64 with a last
-    column of ones, y [K, T, N] float32 or float64."""
+    """One session's RRRGD: a single-session front of the `RRRGD` below, capped at 32 features.  `fit(X, y)` takes
+    standardised device tensors: X [K, T, C+1] float64 with a last column of ones, y [K, T, N] float32 or float64."""
+    _EID = "session"
 
     def __init__(self, n_comp: int = 3, l2: float = 100.):
         self.n_comp, self.l2 = int(n_comp), float(l2)
-        self.flat = None
+        self._m = RRRGD(self.n_comp, self.l2)
         self.losses, self.n_iter, self.func_evals = [], 0, 0
-
-    # views of the flat parameter tensor, ordered [U, b, V] like the reference's ParameterDict
-    def _views(self, flat):
-        N, C, r, T = self.N, self.C, self.n_comp, self.T
-        nu, nb = N * C * r, N * T
-        return flat[:nu].view(N, C, r), flat[nu:nu + nb].view(N, 1, T), flat[nu + nb:].view(r, T)
 
     @property
     def U(self):
-        return self._views(self.flat)[0]
+        return self._m.U(self._EID)
 
     @property
     def b(self):
-        return self._views(self.flat)[1]
+        return self._m.b(self._EID)
 
     @property
     def V(self):
-        return self._views(self.flat)[2]
+        return self._m.V
 
     def _check(self, X, y):
         if X.dim() != 3 or y.dim() != 3 or X.shape[:2] != y.shape[:2]:
@@ -84,56 +81,17 @@ class RRR:
             raise VsError("RRR: X must be float64 (the reference's bias column makes it so)")
 
     def fit(self, X: torch.Tensor, y: torch.Tensor) -> "RRR":
-        """The kernel-side parameters live in one flat float64 tensor ordered [U, b, V]; L-BFGS drives U and V as
-        views of it.  b's master copy is a separate parameter of y's dtype, because the reference's is
-        (rrr.py:44-47: b = mean_k y, float32 when y is): autograd rounds its gradient to that dtype and L-BFGS
-        updates it in that dtype.  Keeping b in float64 instead moves the fit a hundred times further from the
-        reference's than the reference moves under a reordering of its trials, so the
-        closure copies b into the flat tensor before the kernel and db out of it afterwards (N T elements)."""
+        """RRRGD.fit on the one session: the same draw, parameter order [U, b, V] and closure."""
         self._check(X, y)
-        X, y = X.contiguous(), y.contiguous()
-        K, T, C1 = X.shape
-        self.N, self.C, self.T = y.shape[2], C1 - 1, T
-        U0, V0 = init_params(T, self.N, self.C, self.n_comp)
-        dev = X.device
-        b_master = _mean_trials(y).t().unsqueeze(1).contiguous().requires_grad_(True)    # rrr.py:44
-        self.flat = torch.cat([torch.from_numpy(U0).reshape(-1).to(dev), b_master.detach().reshape(-1).double(),
-                               torch.from_numpy(V0).reshape(-1).to(dev)])
-        grad = torch.zeros_like(self.flat)
-        U, b64, V = self._views(self.flat)
-        dU, db64, dV = self._views(grad)
-        U.requires_grad_(True)
-        V.requires_grad_(True)
-        U.grad, V.grad, b_master.grad = dU, dV, torch.zeros_like(b_master)
-        ws = torch.empty(ops.rrr_loss_grad_workspace_bytes(K, T, self.N, self.C) // 8 + 2, dtype=torch.float64,
-                         device=dev)
-        losses = []
-
-        def closure():
-            with torch.no_grad():
-                b64.copy_(b_master)
-                loss = torch.empty(1, dtype=torch.float64, device=dev)
-                ops.rrr_loss_grad(X, y, U, V, b64, self.l2, loss, dU=dU, dV=dV, db=db64, workspace=ws)
-                b_master.grad.copy_(db64)
-            losses.append(loss)
-            return loss[0]
-
-        opt = torch.optim.LBFGS([U, b_master, V])                            # rrr.py:199
-        opt.step(closure)                                                    # rrr.py:177
-        st = opt.state[U]
-        self.n_iter, self.func_evals = int(st["n_iter"]), int(st["func_evals"])
-        self.losses = torch.cat(losses).cpu().numpy()
-        with torch.no_grad():
-            b64.copy_(b_master)
-        self.flat = self.flat.detach()
+        self._m.fit({self._EID: (X, y)})
+        self.N, self.C, self.T = y.shape[2], X.shape[2] - 1, X.shape[1]
+        self.losses, self.n_iter, self.func_evals = self._m.losses, self._m.n_iter, self._m.func_evals
         return self
 
     def mse(self, X: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """sum (yhat - y)^2 over everything: the reference's `mse_val_mean` (rrr.py:180-181), a device scalar."""
         self._check(X, y)
-        loss = torch.empty(1, dtype=torch.float64, device=X.device)
-        ops.rrr_loss_grad(X.contiguous(), y.contiguous(), self.U, self.V, self.b, 0.0, loss)
-        return loss[0]
+        return self._m.mse({self._EID: (X, y)})
 
     def predict(self, X: torch.Tensor) -> torch.Tensor:
         """yhat [K, T, N] (rrr.py:105-116).  Not on the validation path, which never materialises yhat
@@ -146,14 +104,7 @@ class RRR:
         """utils.py:411-447 on the held-out trials: device tensors pred [K, T, N] (clipped rates), bps [N],
         r2 [N], co_bps and r2_mean (scalars)."""
         self._check(X, gt)
-        dev = X.device
-        K, T, N = gt.shape
-        pred = torch.empty(K, T, N, dtype=torch.float64, device=dev) if want_pred else None
-        bps, r2 = (torch.empty(N, dtype=torch.float64, device=dev) for _ in range(2))
-        out = torch.empty(2, dtype=torch.float64, device=dev)
-        ops.rrr_score(X.contiguous(), self.U, self.V, self.b, mean_y.to(torch.float64).contiguous(),
-                      std_y.to(torch.float64).contiguous(), gt.contiguous(), bps, r2, out, pred=pred)
-        return {"pred": pred, "bps": bps, "r2": r2, "co_bps": out[0], "r2_mean": out[1]}
+        return self._m.score(self._EID, X, mean_y, std_y, gt, want_pred=want_pred)
 
     def state_dict(self, eid: str = "session") -> dict:
         """The layout of RRRGD.state_dict (rrr.py:64-71)."""
@@ -261,10 +212,6 @@ def check_dims_wide(C: int, r: int) -> None:
         raise VsError(f"RRRGD: {r} components, supported 1..{MAX_COMPONENTS}")
 
 
-def _is_wide(C: int) -> bool:
-    return C > MAX_FEATURES
-
-
 PIXEL_MAX_FEATURES, PIXEL_MAX_COMPONENTS = ops.RRR_PIXEL_MAX_FEATURES, ops.RRR_PIXEL_MAX_COMPONENTS
 
 
@@ -314,11 +261,21 @@ class PixelFeatures:
         return torch.cat([z, torch.ones(z.shape[0], z.shape[1], 1, dtype=torch.float64, device=z.device)], dim=2)
 
 
-def _pixel_call(fn):
-    """An ops.rrr_pixel_* entry with the leading operand of its wide counterpart."""
-    def call(X, *args, **kw):
-        return fn(X.X, X.idx, X.mean, X.std, *args, **kw)
-    return call
+def _entries(X, N: int, r: int):
+    """(loss_grad, score, workspace bytes of loss_grad) for a session's X, a dense tensor [K, T, C+1] or a
+    PixelFeatures, and N neurons, r components: the ops.rrr*_loss_grad / ops.rrr*_score entry with its leading
+    operands bound, to be called with what follows them (y or U, ...).  C <= 32 runs the narrow entries."""
+    K, T, C1 = X.shape
+    if isinstance(X, PixelFeatures):
+        lead = (X.X, X.idx, X.mean, X.std)
+        return (partial(ops.rrr_pixel_loss_grad, *lead), partial(ops.rrr_pixel_score, *lead),
+                ops.rrr_pixel_loss_grad_workspace_bytes(K, T, N, C1 - 1, r))
+    X = X.contiguous()
+    if C1 - 1 > MAX_FEATURES:
+        return (partial(ops.rrr_wide_loss_grad, X), partial(ops.rrr_wide_score, X),
+                ops.rrr_wide_loss_grad_workspace_bytes(K, T, N, C1 - 1))
+    return (partial(ops.rrr_loss_grad, X), partial(ops.rrr_score, X),
+            ops.rrr_loss_grad_workspace_bytes(K, T, N, C1 - 1))
 
 
 class RRRGD:
@@ -355,15 +312,19 @@ class RRRGD:
     def fit(self, data: dict) -> "RRRGD":
         """One default torch L-BFGS step over [U_0, b_0, U_1, b_1, ..., V] (the reference's ParameterDict order,
         rrr.py:46-49,199).  The initial values are rrr.py:35-49 exactly: one RandomState(0), per session in dict
-        order a U and then a V draw, and the LAST session's V is the one kept.  Each b's master copy has its y's
-        dtype, for the reason in RRR.fit's docstring.  The closure adds the sessions' losses and dVs in session
-        order with plain float64 adds."""
+        order a U and then a V draw, and the LAST session's V is the one kept.  The closure adds the sessions'
+        losses and dVs in session order with plain float64 adds.
+        Each b's master copy is a parameter of its y's dtype, because the reference's is (rrr.py:44-47: b = mean_k y,
+        float32 when y is): autograd rounds its gradient to that dtype and L-BFGS updates it in that dtype.  Keeping
+        b in float64 instead moves the fit a hundred times further from the reference's than the reference moves
+        under a reordering of its trials, so the closure copies b into a float64 tensor
+        before the kernel and db out of one afterwards (N T elements)."""
         if not isinstance(data, dict) or not data:
             raise VsError("RRRGD.fit: {eid: (X, y)} with at least one session")
         sess = {}
         for eid, (X, y) in data.items():
             self._check(X, y)
-            sess[eid] = (X if isinstance(X, PixelFeatures) else X.contiguous(), y.contiguous())
+            sess[eid] = (X, y.contiguous())
         Ts = {X.shape[1] for X, _ in sess.values()}
         if len(Ts) != 1:
             raise VsError(f"RRRGD.fit: the sessions share V, so T must be equal across them (got {sorted(Ts)})")
@@ -374,8 +335,7 @@ class RRRGD:
         U, b_master, b64, dU, db64, dVs, ws, fn = {}, {}, {}, {}, {}, {}, {}, {}
         V0 = None
         for eid, (X, y) in sess.items():
-            K, _, C1 = X.shape
-            N, C = y.shape[2], C1 - 1
+            N, C = y.shape[2], X.shape[2] - 1
             U0 = rs.normal(size=(N, C, r)) / np.sqrt(T * r)                      # rrr.py:42
             V0 = rs.normal(size=(r, T)) / np.sqrt(T * r)                         # rrr.py:43: the last one is kept
             U[eid] = torch.from_numpy(U0).to(dev).requires_grad_(True)
@@ -384,13 +344,7 @@ class RRRGD:
             dU[eid], db64[eid] = torch.zeros_like(U[eid]), torch.zeros_like(b64[eid])
             dVs[eid] = torch.zeros(r, T, dtype=torch.float64, device=dev)
             U[eid].grad, b_master[eid].grad = dU[eid], torch.zeros_like(b_master[eid])
-            wide = _is_wide(C)
-            if isinstance(X, PixelFeatures):
-                fn[eid] = _pixel_call(ops.rrr_pixel_loss_grad)
-                need = ops.rrr_pixel_loss_grad_workspace_bytes(K, T, N, C, r)
-            else:
-                fn[eid] = ops.rrr_wide_loss_grad if wide else ops.rrr_loss_grad
-                need = (ops.rrr_wide_loss_grad_workspace_bytes if wide else ops.rrr_loss_grad_workspace_bytes)(K, T, N, C)
+            fn[eid], _, need = _entries(X, N, r)
             ws[eid] = torch.empty(need // 8 + 2, dtype=torch.float64, device=dev)
         V = torch.from_numpy(V0).to(dev).requires_grad_(True)
         V.grad = torch.zeros_like(V)
@@ -399,10 +353,10 @@ class RRRGD:
         def closure():
             with torch.no_grad():
                 total = None
-                for i, (eid, (X, y)) in enumerate(sess.items()):
+                for i, (eid, (_, y)) in enumerate(sess.items()):
                     b64[eid].copy_(b_master[eid])
                     loss = torch.empty(1, dtype=torch.float64, device=dev)
-                    fn[eid](X, y, U[eid], V, b64[eid], self.l2, loss, dU=dU[eid], dV=dVs[eid], db=db64[eid],
+                    fn[eid](y, U[eid], V, b64[eid], self.l2, loss, dU=dU[eid], dV=dVs[eid], db=db64[eid],
                             workspace=ws[eid])
                     b_master[eid].grad.copy_(db64[eid])
                     if i == 0:
@@ -459,12 +413,7 @@ class RRRGD:
         for eid, (X, y) in data.items():
             self._check_session(eid, X, y, "RRRGD.mse")
             loss = torch.empty(1, dtype=torch.float64, device=X.device)
-            if isinstance(X, PixelFeatures):
-                fn = _pixel_call(ops.rrr_pixel_loss_grad)
-            else:
-                fn = ops.rrr_wide_loss_grad if _is_wide(X.shape[2] - 1) else ops.rrr_loss_grad
-                X = X.contiguous()
-            fn(X, y.contiguous(), self._U[eid], self._V, self._b[eid], 0.0, loss)
+            _entries(X, y.shape[2], self.n_comp)[0](y.contiguous(), self._U[eid], self._V, self._b[eid], 0.0, loss)
             total = loss if total is None else total + loss
         if total is None:
             raise VsError("RRRGD.mse: {eid: (X, y)} with at least one session")
@@ -480,13 +429,8 @@ class RRRGD:
         pred = torch.empty(K, T, N, dtype=torch.float64, device=dev) if want_pred else None
         bps, r2 = (torch.empty(N, dtype=torch.float64, device=dev) for _ in range(2))
         out = torch.empty(2, dtype=torch.float64, device=dev)
-        if isinstance(X, PixelFeatures):
-            fn = _pixel_call(ops.rrr_pixel_score)
-        else:
-            fn = ops.rrr_wide_score if _is_wide(X.shape[2] - 1) else ops.rrr_score
-            X = X.contiguous()
-        fn(X, self._U[eid], self._V, self._b[eid], mean_y.to(torch.float64).contiguous(),
-           std_y.to(torch.float64).contiguous(), gt.contiguous(), bps, r2, out, pred=pred)
+        _entries(X, N, self.n_comp)[1](self._U[eid], self._V, self._b[eid], mean_y.to(torch.float64).contiguous(),
+                                       std_y.to(torch.float64).contiguous(), gt.contiguous(), bps, r2, out, pred=pred)
         return {"pred": pred, "bps": bps, "r2": r2, "co_bps": out[0], "r2_mean": out[1]}
 
     def state_dict(self) -> dict:
