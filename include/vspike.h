@@ -213,6 +213,24 @@ int vs_attn_bwd(int32_t dtype, int64_t B, int64_t N, int64_t H, int64_t Dh, cons
                 void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same attention for head dim 32 and short sequences, 1 <= N <= 256 (the MAE decoder: 512 wide,
+ * 16 heads, 82 or 197 tokens); since ABI v15.  Semantics and layout are vs_attn_fwd / vs_attn_bwd with
+ * 32 in place of 64: qkv [B*N, 3*H*32] rows, Q of head h at column 32h, K at 32(H+h), V at 32(2H+h);
+ * o [B*N, H*32]; lse [B, H, N] f32 natural log.  A head's K and V stay on the chip, so these are not
+ * flash kernels: a plain row maximum, no redo pass, no atomics, every sum in an order fixed by the
+ * extents (two calls give equal bits).  VS_BF16 runs MFMA kernels, VS_F32 exact f32 ones.  N > 256
+ * returns VS_EINVAL and launches nothing.  Rows must be 16-byte aligned (bf16: ld % 8 == 0 for inputs,
+ * ld % 4 == 0 and 8-byte alignment for o / dqkv; f32: ld % 4 == 0).  workspace: f32 scratch of
+ * vs_attn32_bwd_workspace_bytes() (delta [B, H, N], written and read by the f32 kernels only).
+ * ------------------------------------------------------------------------------------------ */
+int vs_attn32_fwd(int32_t dtype, int64_t B, int64_t N, int64_t H, const void* qkv, int64_t ld_qkv, void* o,
+                  int64_t ld_o, float* lse, float scale, void* stream);
+size_t vs_attn32_bwd_workspace_bytes(int64_t B, int64_t N, int64_t H);
+int vs_attn32_bwd(int32_t dtype, int64_t B, int64_t N, int64_t H, const void* qkv, int64_t ld_qkv,
+                  const void* o, int64_t ld_o, const void* dout, int64_t ld_do, const float* lse,
+                  void* dqkv, int64_t ld_dqkv, void* workspace, float scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-device video preprocessing, the VideoMAE plugin's forward prologue (videomae.py:18-25):
  * frame gather video[:, frame_idx] -> gray repeated to 3 channels -> the HF image processor's
  * resize (shortest edge -> out_size, PIL BILINEAR on uint8 frames, reproduced bit-exactly:
@@ -321,6 +339,9 @@ int vs_spike_metrics(int64_t trials, int64_t T, int64_t N, const float* gt, cons
  * out-proj + residual -> LN2 -> fc1+GELU -> fc2 + residual, and its backward.  All tensors are
  * caller-owned; `dtype` is the activation/weight element type (residual stream, LN statistics,
  * softmax statistics and gradients of weights are f32 in both modes).
+ * hidden is heads * 64 (vs_attn_fwd / vs_attn_bwd) or, since ABI v15, heads * 32 with at most 256
+ * tokens and dtype f32 or bf16 (vs_attn32_fwd / vs_attn32_bwd; attn_ws then holds
+ * vs_attn32_bwd_workspace_bytes); attn_scale is the caller's in both cases.
  * ------------------------------------------------------------------------------------------ */
 typedef struct vs_vit_layer {
   int32_t dtype;
@@ -377,7 +398,7 @@ typedef struct vs_vit_layer_grad {
   float* dy;  void* dy_lp;                       /* [M, D] f32 + dtype copy */
   void* d_o;            /* [M, D] dtype */
   void* d_qkv;          /* [M, 3D] dtype */
-  void* attn_ws;        /* vs_attn_bwd_workspace_bytes */
+  void* attn_ws;        /* vs_attn_bwd_workspace_bytes (hidden == heads * 32: vs_attn32_bwd_workspace_bytes) */
   void* ln_ws;          /* vs_layernorm_bwd_workspace_bytes(M, D) */
   void* gemm_ws;        /* split-K partials of the weight-gradient GEMMs (optional) */
   int64_t gemm_ws_bytes;
@@ -558,6 +579,45 @@ size_t vs_info_nce_workspace_bytes(int64_t n, int64_t m);
 int vs_info_nce(int64_t n, int64_t m, int64_t E, const float* ref, const float* pos, const float* neg,
                 const float* log_inv_tau, float* out, float* d_ref, float* d_pos, float* d_neg, float grad_scale,
                 float* d_log_inv_tau, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Masked-autoencoder pieces (csrc/mae.hip, since ABI v15): what HF ViTMAEForPreTraining adds around the
+ * encoder and decoder blocks.  G images, P patches each, Lk kept (1 <= Lk <= P), D channels (D % 4 == 0, f32
+ * rows 16-byte aligned).  The index tensors are the host's int32 device tensors: ids_keep [G, Lk] = the first
+ * Lk columns of argsort(noise), ids_restore [G, P] = argsort of that argsort; patch p of image g is kept iff
+ * ids_restore[g, p] < Lk and is then token 1 + ids_restore[g, p] of the encoder's sequence.  An index outside
+ * its range selects nothing (zeros): it is never used as an address.  Every sum runs in an order fixed by the
+ * extents (no atomics).
+ *   vs_mae_embed_fwd         x0[g, 0] = cls + table[0]; x0[g, 1 + j] = patches[g, ids_keep[g, j]]
+ *                            (patches [G*P, D] f32 already carry their position rows; x0 [G, Lk + 1, D] f32)
+ *   vs_mae_embed_bwd         d_patches [G*P, D] (out_dtype) = the kept rows of dx [G, Lk + 1, D] f32, zero rows for
+ *                            masked patches; d_cls [D] = sum_g dx[g, 0], ascending g (written, not accumulated)
+ *   vs_mae_dec_assemble_fwd  xd[g, 0] = e[g, 0] + tabd[0]; xd[g, 1 + p] = (kept ? e[g, 1 + ids_restore[g, p]] :
+ *                            mask_token) + tabd[1 + p]   (e [G, Lk + 1, D] f32, tabd [P + 1, D], xd [G, P + 1, D])
+ *   vs_mae_dec_assemble_bwd  d_e [G, Lk + 1, D] (out_dtype): row 0 = dxd[g, 0], row 1 + j = dxd[g, 1 + ids_keep[g, j]];
+ *                            d_mask_token [D] = sum over the masked (g, p), ascending p then ascending g (written);
+ *                            workspace: vs_mae_dec_assemble_bwd_workspace_bytes(G, D), 16-byte aligned
+ *   vs_mae_recon_loss        pred [G, P + 1, K] f32 (row 0 of an image, the CLS row, is ignored), K = patch^2 * C,
+ *                            P = (S / patch)^2, 1 <= Lk < P; target = HF's patchify of the f32 pixels [G, C, S, S]
+ *                            (k = (i * patch + j) * C + c).  loss[0] = sum_masked mean_k (pred - target)^2 /
+ *                            n_masked with n_masked = G (P - Lk), accumulated in f64; d_pred [G, P + 1, K]
+ *                            (out_dtype) = 2 (pred - target) / (K n_masked) on masked rows, zeros on kept and CLS
+ *                            rows.  workspace: vs_mae_recon_loss_workspace_bytes(G, P), 8-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int vs_mae_embed_fwd(int64_t G, int64_t P, int64_t Lk, int64_t D, const float* patches, const int32_t* ids_keep,
+                     const float* cls, const float* table, float* x0, void* stream);
+int vs_mae_embed_bwd(int32_t out_dtype, int64_t G, int64_t P, int64_t Lk, int64_t D, const float* dx,
+                     const int32_t* ids_restore, float* d_cls, void* d_patches, void* stream);
+int vs_mae_dec_assemble_fwd(int64_t G, int64_t P, int64_t Lk, int64_t D, const float* e, const int32_t* ids_restore,
+                            const float* mask_token, const float* tabd, float* xd, void* stream);
+size_t vs_mae_dec_assemble_bwd_workspace_bytes(int64_t G, int64_t D);
+int vs_mae_dec_assemble_bwd(int32_t out_dtype, int64_t G, int64_t P, int64_t Lk, int64_t D, const float* dxd,
+                            const int32_t* ids_keep, const int32_t* ids_restore, void* d_e, float* d_mask_token,
+                            void* workspace, void* stream);
+size_t vs_mae_recon_loss_workspace_bytes(int64_t G, int64_t P);
+int vs_mae_recon_loss(int32_t out_dtype, int64_t G, int64_t C, int64_t S, int64_t patch, int64_t Lk,
+                      const float* pred, int64_t ld_pred, const float* pixels, const int32_t* ids_restore,
+                      float* loss, void* d_pred, int64_t ld_dpred, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Reduced-rank regression validation of the contrastive path (csrc/rrr.hip):

@@ -109,7 +109,7 @@ ScopedTimer::~ScopedTimer() {
 // 11: vs_contrast_frames (csrc/contrast_loader.hip)
 // 12: vs_rrr_pixel_* (csrc/rrr_pixel.hip) and vs_rrr_pixel_dispatch_counts
 // 13: vs_flow_median2, vs_flow_quantiles, vs_flow_clip_mean, vs_motion_energy, vs_flow_plan (csrc/flow_features.hip)
-extern "C" int vs_version(void) { return 14; }
+extern "C" int vs_version(void) { return 15; }
 extern "C" const char* vs_build_id(void) { return VS_BUILD_ID; }
 
 extern "C" int vs_knob_get(int k) {

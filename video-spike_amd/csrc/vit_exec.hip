@@ -67,6 +67,8 @@ static int stream_wait(hipStream_t from, hipStream_t to, hipEvent_t ev) {
 // a_pre == NULL selects the fused MLP (vs_mlp_fwd / vs_mlp_bwd_da): bf16, a shape vs_mlp_fused_ok
 // accepts; a_act then points at [M, F] bf16 scratch that the BACKWARD writes (gelu(pre) for dW2)
 static bool mlp_fused(const vs_vit_layer* L) { return L->a_pre == nullptr; }
+// head dim 32: the short-sequence kernels (vs_attn32_fwd / vs_attn32_bwd) in place of the flash kernels
+static bool head32(const vs_vit_layer* L) { return L->heads > 0 && L->hidden == L->heads * 32; }
 
 // MX-FP8 scratch of one block forward (the A operand of the product being run, its scales, the
 // weight and its scales; reused product by product in stream order)
@@ -107,7 +109,9 @@ static int check_layer(const vs_vit_layer* L) {
                                     (size_t)L->fp8_ws_bytes >= vs_vit_fp8_workspace_bytes(L->batch * L->tokens,
                                                                                            L->hidden, L->mlp)),
              "vs_vit_layer: VS_FP8 needs hidden % 128 == 0, mlp % 128 == 0 and the fp8 workspace");
-  VS_REQUIRE(L->hidden == L->heads * 64, "vs_vit_layer: hidden must be heads*64");
+  VS_REQUIRE(L->hidden == L->heads * 64 || L->hidden == L->heads * 32, "vs_vit_layer: hidden must be heads*64 or heads*32");
+  VS_REQUIRE(!head32(L) || (L->tokens <= 256 && L->dtype != VS_FP8),
+             "vs_vit_layer: hidden == heads*32 needs at most 256 tokens and dtype f32 or bf16 (vs_attn32)");
   VS_REQUIRE(L->batch > 0 && L->tokens > 0 && L->mlp > 0, "vs_vit_layer: empty");
   VS_REQUIRE(!mlp_fused(L) || (L->dtype == VS_BF16 && vs_mlp_fused_ok(L->batch * L->tokens, L->hidden, L->mlp) &&
                                L->a_act),
@@ -140,7 +144,10 @@ extern "C" int vs_vit_layer_fwd(const vs_vit_layer* L, void* stream) {
     g.bias = L->b_qkv;
     VS_CALL(product(g));
   }
-  VS_CALL(vs_attn_fwd(T, L->batch, L->tokens, L->heads, 64, L->qkv, 3 * D, L->attn_o, D, L->lse, L->attn_scale, stream));
+  if (head32(L))
+    VS_CALL(vs_attn32_fwd(T, L->batch, L->tokens, L->heads, L->qkv, 3 * D, L->attn_o, D, L->lse, L->attn_scale, stream));
+  else
+    VS_CALL(vs_attn_fwd(T, L->batch, L->tokens, L->heads, 64, L->qkv, 3 * D, L->attn_o, D, L->lse, L->attn_scale, stream));
   {
     vs_gemm_desc g = gdesc(T, VS_F32, true, true, M, D, D, L->attn_o, D, L->w_proj, D, L->y, D,
                            VS_EPI_BIAS | VS_EPI_RESIDUAL);
@@ -295,8 +302,12 @@ extern "C" int vs_vit_layer_bwd(const vs_vit_layer* L, const vs_vit_layer_grad* 
     VS_CALL(vs_gemm(&g, stream));
   }
   VS_CALL(wait_prev(3));  // d_qkv is read by the previous block's dWqkv
-  VS_CALL(vs_attn_bwd(T, L->batch, L->tokens, L->heads, 64, L->qkv, 3 * D, L->attn_o, D, G->d_o, D, L->lse, G->d_qkv,
-                      3 * D, G->attn_ws, L->attn_scale, stream));
+  if (head32(L))
+    VS_CALL(vs_attn32_bwd(T, L->batch, L->tokens, L->heads, L->qkv, 3 * D, L->attn_o, D, G->d_o, D, L->lse, G->d_qkv,
+                          3 * D, G->attn_ws, L->attn_scale, stream));
+  else
+    VS_CALL(vs_attn_bwd(T, L->batch, L->tokens, L->heads, 64, L->qkv, 3 * D, L->attn_o, D, G->d_o, D, L->lse, G->d_qkv,
+                        3 * D, G->attn_ws, L->attn_scale, stream));
   VS_CALL(fork(3));  // dqkv ready
   {  // [side] dWqkv[3D,D] += dqkv^T h1;  d(q,k,v bias) += colsum(dqkv) fused
     vs_gemm_desc g = gdesc(T, VS_F32, false, false, 3 * D, D, M, G->d_qkv, 3 * D, L->h1, D, G->w_qkv, D, VS_EPI_ATOMIC);

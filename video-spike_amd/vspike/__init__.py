@@ -8,6 +8,7 @@ from .behaviour import behaviour_rrr_data, flow_features, get_rrr_data
 from .contrast import ContrastViT
 from .config import DictConfig, config_from_kwargs, load_run_config, update_config
 from .linear import Linear
+from .mae import MAE
 from .loss import InfoNCE, MSEMeanLoss, PoissonNLLMeanLoss, make_criterion, mse_mean, poisson_nll_mean
 from .optim import FusedAdamW
 from .pca import PCA, pca_embedding, pca_rrr_data
@@ -25,8 +26,10 @@ NAME2MODEL = {
     "VideoMAETemporal": VideoMAETemporal,
     # the reference's contrastive pretraining model (src/model/vit_mae/vit_mae.py:26-44, `pretrain.py --model c`)
     "ContrastViT": ContrastViT,
+    # the reference's masked-autoencoder pretraining model (vit_mae.py:45-94, `pretrain.py --model m`)
+    "MAE": MAE,
 }
 
-__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "ContrastViT", "InfoNCE", "RRR", "train_rrr", "RRRGD", "prepare_rrr_inputs", "train_rrr_baseline", "PixelFeatures", "pixel_rrr_data", "PCA", "pca_embedding", "pca_rrr_data", "flow_features", "get_rrr_data", "behaviour_rrr_data", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
+__all__ = ["NAME2MODEL", "Linear", "VideoMAE", "VideoMAETemporal", "R3D", "ContrastViT", "MAE", "InfoNCE", "RRR", "train_rrr", "RRRGD", "prepare_rrr_inputs", "train_rrr_baseline", "PixelFeatures", "pixel_rrr_data", "PCA", "pca_embedding", "pca_rrr_data", "flow_features", "get_rrr_data", "behaviour_rrr_data", "FusedAdamW", "poisson_nll_mean", "PoissonNLLMeanLoss",
            "mse_mean", "MSEMeanLoss", "make_criterion",
            "DictConfig", "update_config", "config_from_kwargs", "load_run_config"]

@@ -147,6 +147,10 @@ PROTOTYPES = {
     "vs_attn_redo_count": (ctypes.c_int, [ctypes.POINTER(c_i64), c_i32]),
     "vs_attn_bwd": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p,
                                    c_p, c_i64, c_p, c_f32, c_p]),
+    "vs_attn32_fwd": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_f32, c_p]),
+    "vs_attn32_bwd_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "vs_attn32_bwd": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64,
+                                     c_p, c_f32, c_p]),
     "vs_patch_im2col": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
     "vs_sinusoid_table": (ctypes.c_int, [c_i64, c_i64, c_p, c_p]),
     "vs_patch_embed_fwd": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64,
@@ -202,6 +206,14 @@ PROTOTYPES = {
                                          c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "vs_info_nce_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "vs_info_nce": (ctypes.c_int, [c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f32, c_p, c_p, c_p]),
+    "vs_mae_embed_fwd": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "vs_mae_embed_bwd": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "vs_mae_dec_assemble_fwd": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "vs_mae_dec_assemble_bwd_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "vs_mae_dec_assemble_bwd": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "vs_mae_recon_loss_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "vs_mae_recon_loss": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p,
+                                         c_i64, c_p, c_p]),
     "vs_rrr_loss_grad_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
     "vs_rrr_loss_grad": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i32, c_p, c_p, c_p, c_f64, c_p,
                                         c_p, c_p, c_p, c_p, c_p]),

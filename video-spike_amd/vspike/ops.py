@@ -238,6 +238,29 @@ def attn_bwd(qkv, o, dout, lse, dqkv, workspace, B, N, H, scale=0.125):
     return dqkv
 
 
+def attn32_fwd(qkv, o, lse, B, N, H, scale=None):
+    """Head-dim-32 attention for 1 <= N <= 256 (vs_attn32_fwd): qkv [B*N, >= 3*H*32], o [B*N, >= H*32], lse
+    [B, H, N] f32.  scale defaults to 1 / sqrt(32)."""
+    require_device(qkv, o, lse)
+    scale = attn_scale(32) if scale is None else scale
+    check(lib().vs_attn32_fwd(L.dtype_code(qkv.dtype), B, N, H, qkv.data_ptr(), qkv.stride(0), o.data_ptr(),
+                              o.stride(0), lse.data_ptr(), scale, stream()), "vs_attn32_fwd")
+    return o
+
+
+def attn32_bwd_workspace_bytes(B, N, H):
+    return int(lib().vs_attn32_bwd_workspace_bytes(B, N, H))
+
+
+def attn32_bwd(qkv, o, dout, lse, dqkv, workspace, B, N, H, scale=None):
+    require_device(qkv, o, dout, lse, dqkv, workspace)
+    scale = attn_scale(32) if scale is None else scale
+    check(lib().vs_attn32_bwd(L.dtype_code(qkv.dtype), B, N, H, qkv.data_ptr(), qkv.stride(0), o.data_ptr(),
+                              o.stride(0), dout.data_ptr(), dout.stride(0), lse.data_ptr(), dqkv.data_ptr(),
+                              dqkv.stride(0), workspace.data_ptr(), scale, stream()), "vs_attn32_bwd")
+    return dqkv
+
+
 def patch_im2col(pixels, cols, tubelet, patch):
     require_device(pixels, cols)
     B, F, C, H, W = pixels.shape
@@ -359,6 +382,107 @@ def cls_embed_bwd(dx, d_cls, d_patches):
     check(lib().vs_cls_embed_bwd(L.dtype_code(d_patches.dtype), G, T - 1, D, dx.data_ptr(), d_cls.data_ptr(),
                                  d_patches.data_ptr(), stream()), "vs_cls_embed_bwd")
     return d_patches
+
+
+def _mae_ids(ids, shape, what):
+    if ids.dtype != torch.int32 or tuple(ids.shape) != tuple(shape) or not ids.is_contiguous():
+        raise L.VsError(f"{what}: the index tensor must be a dense int32 {tuple(shape)}")
+
+
+def _mae_dense(what, *tensors):
+    for t in tensors:
+        if not t.is_contiguous():
+            raise L.VsError(f"{what}: tensors must be dense")
+
+
+def mae_embed_fwd(patches, ids_keep, cls, table, x0):
+    """x0 [G, Lk+1, D] f32: row 0 = cls + table[0], row 1 + j = patches[g * P + ids_keep[g, j]] (vs_mae_embed_fwd).
+    patches [G*P, D] f32, ids_keep [G, Lk] int32, table [>= 1, D] (row 0 is read)."""
+    require_device(patches, ids_keep, cls, table, x0)
+    G, T, D = x0.shape
+    P = patches.shape[0] // G
+    if patches.shape != (G * P, D) or cls.numel() != D or table.shape[-1] != D or x0.dtype != torch.float32:
+        raise L.VsError("mae_embed_fwd: patches [G*P, D], cls [D], table [., D], x0 [G, Lk+1, D] f32")
+    _mae_ids(ids_keep, (G, T - 1), "mae_embed_fwd")
+    _mae_dense("mae_embed_fwd", patches, table, x0)
+    check(lib().vs_mae_embed_fwd(G, P, T - 1, D, patches.data_ptr(), ids_keep.data_ptr(), cls.data_ptr(),
+                                 table.data_ptr(), x0.data_ptr(), stream()), "vs_mae_embed_fwd")
+    return x0
+
+
+def mae_embed_bwd(dx, ids_restore, d_cls, d_patches):
+    """d_patches [G*P, D] (f32 or bf16) = the kept rows of dx [G, Lk+1, D] f32 (zero rows for masked patches), d_cls [D]
+    = sum over images (ascending) of dx[:, 0] (vs_mae_embed_bwd).  ids_restore [G, P] int32."""
+    require_device(dx, ids_restore, d_cls, d_patches)
+    G, T, D = dx.shape
+    P = ids_restore.shape[1]
+    if d_patches.shape != (G * P, D) or d_cls.numel() != D or dx.dtype != torch.float32:
+        raise L.VsError("mae_embed_bwd: dx [G, Lk+1, D] f32, d_cls [D], d_patches [G*P, D]")
+    _mae_ids(ids_restore, (G, P), "mae_embed_bwd")
+    _mae_dense("mae_embed_bwd", dx, d_patches)
+    check(lib().vs_mae_embed_bwd(L.dtype_code(d_patches.dtype), G, P, T - 1, D, dx.data_ptr(), ids_restore.data_ptr(),
+                                 d_cls.data_ptr(), d_patches.data_ptr(), stream()), "vs_mae_embed_bwd")
+    return d_patches
+
+
+def mae_dec_assemble_fwd(e, ids_restore, mask_token, tabd, xd):
+    """xd [G, P+1, D] f32 from e [G, Lk+1, D] f32: the decoder's sequence (vs_mae_dec_assemble_fwd)."""
+    require_device(e, ids_restore, mask_token, tabd, xd)
+    G, T, D = xd.shape
+    if e.shape[0] != G or e.shape[2] != D or tabd.shape != (T, D) or mask_token.numel() != D or \
+            e.dtype != torch.float32 or xd.dtype != torch.float32:
+        raise L.VsError("mae_dec_assemble_fwd: e [G, Lk+1, D] f32, mask_token [D], tabd [P+1, D], xd [G, P+1, D] f32")
+    _mae_ids(ids_restore, (G, T - 1), "mae_dec_assemble_fwd")
+    _mae_dense("mae_dec_assemble_fwd", e, tabd, xd)
+    check(lib().vs_mae_dec_assemble_fwd(G, T - 1, e.shape[1] - 1, D, e.data_ptr(), ids_restore.data_ptr(),
+                                        mask_token.data_ptr(), tabd.data_ptr(), xd.data_ptr(), stream()),
+          "vs_mae_dec_assemble_fwd")
+    return xd
+
+
+def mae_dec_assemble_bwd_workspace_bytes(G, D):
+    return int(lib().vs_mae_dec_assemble_bwd_workspace_bytes(G, D))
+
+
+def mae_dec_assemble_bwd(dxd, ids_keep, ids_restore, d_e, d_mask_token, workspace):
+    """d_e [G, Lk+1, D] (f32 or bf16) and d_mask_token [D] f32 (written) from dxd [G, P+1, D] f32
+    (vs_mae_dec_assemble_bwd); workspace: f32, mae_dec_assemble_bwd_workspace_bytes(G, D)."""
+    require_device(dxd, ids_keep, ids_restore, d_e, d_mask_token, workspace)
+    G, T, D = dxd.shape
+    Lk = d_e.shape[1] - 1
+    if d_e.shape != (G, Lk + 1, D) or d_mask_token.numel() != D or dxd.dtype != torch.float32 or \
+            workspace.numel() * workspace.element_size() < mae_dec_assemble_bwd_workspace_bytes(G, D):
+        raise L.VsError("mae_dec_assemble_bwd: dxd [G, P+1, D] f32, d_e [G, Lk+1, D], d_mask_token [D], workspace")
+    _mae_ids(ids_keep, (G, Lk), "mae_dec_assemble_bwd")
+    _mae_ids(ids_restore, (G, T - 1), "mae_dec_assemble_bwd")
+    _mae_dense("mae_dec_assemble_bwd", dxd, d_e)
+    check(lib().vs_mae_dec_assemble_bwd(L.dtype_code(d_e.dtype), G, T - 1, Lk, D, dxd.data_ptr(), ids_keep.data_ptr(),
+                                        ids_restore.data_ptr(), d_e.data_ptr(), d_mask_token.data_ptr(),
+                                        workspace.data_ptr(), stream()), "vs_mae_dec_assemble_bwd")
+    return d_e
+
+
+def mae_recon_loss_workspace_bytes(G, P):
+    return int(lib().vs_mae_recon_loss_workspace_bytes(G, P))
+
+
+def mae_recon_loss(pred, pixels, ids_restore, len_keep, patch, loss, d_pred, workspace):
+    """HF ViTMAE's forward_loss (norm_pix_loss false) and its gradient (vs_mae_recon_loss): pred [G, P+1, K] f32 (the
+    CLS row is ignored), pixels [G, C, S, S] f32, loss [1] f32, d_pred [G, P+1, K] f32 or bf16."""
+    require_device(pred, pixels, ids_restore, loss, d_pred, workspace)
+    G, C, S, _ = pixels.shape
+    P = (S // patch) ** 2
+    K = patch * patch * C
+    if pred.shape != (G, P + 1, K) or d_pred.shape != (G, P + 1, K) or pred.dtype != torch.float32 or \
+            pixels.dtype != torch.float32 or pixels.shape[3] != S or \
+            workspace.numel() * workspace.element_size() < mae_recon_loss_workspace_bytes(G, P):
+        raise L.VsError("mae_recon_loss: pred / d_pred [G, P+1, patch^2 C], pixels [G, C, S, S] f32, workspace")
+    _mae_ids(ids_restore, (G, P), "mae_recon_loss")
+    _mae_dense("mae_recon_loss", pred, pixels, d_pred)
+    check(lib().vs_mae_recon_loss(L.dtype_code(d_pred.dtype), G, C, S, patch, int(len_keep), pred.data_ptr(), K,
+                                  pixels.data_ptr(), ids_restore.data_ptr(), loss.data_ptr(), d_pred.data_ptr(), K,
+                                  workspace.data_ptr(), stream()), "vs_mae_recon_loss")
+    return loss
 
 
 def embed_head_fwd(x, ldx, gamma, beta, eps, w, b, h, mean, rstd, z_raw, nrm, z):

@@ -204,6 +204,32 @@ EMBEDDING_MODS = ("cebra", "pca", "ws", "whisker-video", "vit", "cm", "m", "c") 
 INPUT_MODS = ("me", "of", "of-2d", "of-2d-v", "all", "other", "me-all", "of-all") + EMBEDDING_MODS
 
 
+def train_rrr_wide(data_dict: dict, device=None, n_comp: int = 3, l2: float = 100.) -> dict:
+    """train_rrr for embeddings of 33 .. 1024 features (the MAE plugin's hidden_size-wide z): the same preparation
+    (the train split's `_std`, the bias column), then one RRRGD session per eid in place of RRR, which takes at most
+    32 features.  Same return value as train_rrr."""
+    result = {}
+    for eid, d in data_dict.items():
+        X = [_device_tensor(x, device or (x.device if torch.is_tensor(x) and x.is_cuda else "cuda")) for x in d["X"]]
+        dev = X[0].device
+        y = [_device_tensor(v, dev) for v in d["y"]]
+        mean_X, std_X = _std(X[0])
+        mean_y, std_y = _std(y[0])
+        Xs, ys = [], []
+        for i in range(2):
+            x = _div(X[i] - mean_X, std_X).to(torch.float64)
+            ones = torch.ones(x.shape[0], x.shape[1], 1, dtype=torch.float64, device=dev)
+            Xs.append(torch.cat([x, ones], dim=2))
+            ys.append(_div(y[i] - mean_y, std_y))
+        if isinstance(d.get("setup"), dict):
+            d["setup"].update(mean_X_Tv=mean_X, std_X_Tv=std_X, mean_y_TN=mean_y, std_y_TN=std_y)
+        model = RRRGD(n_comp=n_comp, l2=l2).fit({eid: (Xs[0], ys[0])})
+        s = model.score(eid, Xs[1], mean_y, std_y, y[1])
+        result[eid] = {"gt": y[1].cpu().numpy(), "pred": s["pred"].cpu().numpy(),
+                       "bps": s["bps"].cpu().tolist(), "r2": s["r2"].cpu().tolist(), "eid": eid}
+    return result
+
+
 def check_dims_wide(C: int, r: int) -> None:
     if not 1 <= C <= WIDE_MAX_FEATURES:
         raise VsError(f"RRRGD: {C} features, supported 1..{WIDE_MAX_FEATURES} (the bias column not counted); "

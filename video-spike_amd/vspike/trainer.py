@@ -97,16 +97,30 @@ class ContrastTrainer:
         res["loss"].backward()
         return self._finish(res)
 
+    def step_recon(self, ref) -> dict:
+        """The reference's step for the `MAE` model (contrast.py:100-107 with `loss_fn_`'s first branch): one forward
+        of `ref`, loss = recon_loss, backward, update.  Returns {'loss'} detached."""
+        res = {"loss": self.model(ref)["recon_loss"]}
+        res["loss"].backward()
+        return self._finish(res)
+
     @torch.no_grad()
     def transform(self, batches: Iterable) -> torch.Tensor:
         """`src/trainer/contrast.py:165-206`: the stacked embeddings z of every batch (tensors, or dicts
-        with the images under 'ref'), in order.  The model's train / eval mode is restored afterwards."""
+        with the images under 'ref'), in order, with `model.config.mask_ratio` set to 0 for the pass
+        (contrast.py:177-202).  The mask ratio and the model's train / eval mode are restored afterwards."""
         was_training = self.model.training
+        conf = getattr(self.model, "config", None)
+        ratio = getattr(conf, "mask_ratio", None)
         self.model.eval()
+        if ratio is not None:
+            conf.mask_ratio = 0
         try:
             zs = [self.model(b["ref"] if isinstance(b, dict) else b)["z"] for b in batches]
         finally:
             self.model.train(was_training)
+            if ratio is not None:
+                conf.mask_ratio = ratio
         return torch.cat(zs, dim=0)
 
     @torch.no_grad()
@@ -120,7 +134,7 @@ class ContrastTrainer:
         sort(choice(F - 1, T, replace=False)) (at F = 120, T = 100 its `choice(119, 100)`, last frame never used).
         The embeddings stay on the device between the transform and the fit."""
         import numpy as np
-        from .rrr import train_rrr
+        from .rrr import train_rrr, train_rrr_wide
         X, y = [], []
         for batches in (train_batches, val_batches):
             batches = list(batches)
@@ -136,7 +150,8 @@ class ContrastTrainer:
         if sel.numel() != T:
             raise ValueError(f"ContrastTrainer.validate: {sel.numel()} frame indices for {T} time bins")
         data = {eid: {"X": [x[:, sel, :] for x in X], "y": y, "setup": {}}}
-        res = train_rrr(data)
+        # an embedding wider than train_rrr's 32 features (MAE's hidden_size-wide z) goes through one RRRGD session
+        res = (train_rrr_wide if X[0].shape[-1] > 32 else train_rrr)(data)
         return {"val_bps": float(np.nanmean(res[eid]["bps"]))}
 
 
@@ -150,12 +165,16 @@ class ContrastTrainer:
         Returns {'steps': the per-step loss dicts (device tensors: nothing is read back per step), 'val_bps': one per
         pass, 'best_val_bps', 'best_pass'}.  No wandb, no progress bar."""
         steps, vals, best, best_pass = [], [], -float("inf"), None
+        from .mae import MAE
         fused = getattr(loader, "fused", None)
+        recon = isinstance(self.model, MAE)
         self.model.train()
         while len(steps) < max_steps:
             before = len(steps)
             for batch in loader:
-                if fused is not None:
+                if recon:       # the loader still drew pos and neg: numpy's generator stands where the reference's does
+                    steps.append(self.step_recon(batch["ref"]))
+                elif fused is not None:
                     steps.append(self.step_fused(fused(batch), batch["ref"].shape[0]))
                 else:
                     steps.append(self.step(batch["ref"], batch["pos"], batch["neg"]))
