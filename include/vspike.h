@@ -198,6 +198,21 @@ int vs_mlp_bwd_da(int64_t M, int64_t D, int64_t F, const void* h2, int64_t ldh, 
  * Backward writes dQ, dK, dV into dqkv (same layout as qkv); workspace is f32 scratch of
  * vs_attn_bwd_workspace_bytes().  dtype VS_BF16 runs the MFMA flash kernels; VS_F32 runs exact
  * f32 reference-grade kernels (the 1e-4 parity mode).
+ * Contract (tests/test_gpu_attn_contract.py): Dh must be 64, B, N, H >= 1; the four leading dimensions
+ * ld_qkv, ld_o, ld_do, ld_dqkv are independent, each at least its row width (3*H*64 or H*64), in
+ * elements; scale is the caller's (the kernels fold it with log2 e into a bf16 pre-scaling of Q or K and
+ * multiply it into dQ and dK).  Row alignment, VS_BF16: qkv, dout and o (as the forward's output and as
+ * the backward's input) are accessed as 16-byte vectors, so ld_qkv, ld_do, ld_o % 8 == 0 and 16-byte
+ * aligned bases; dqkv is stored as 8-byte vectors, ld_dqkv % 4 == 0 and an 8-byte aligned base; the
+ * workspace 16-byte aligned.  VS_F32: element accesses only, any leading dimension (odd ones too).  lse is
+ * contiguous [B, H, N] f32 in both modes.  A call that breaks any of this returns VS_EINVAL with
+ * vs_last_error() set, launches nothing and counts no dispatch.
+ * Memory: the forward reads qkv rows 0 .. B*N-1 and writes exactly the B*N x H*64 elements of o and the
+ * B*H*N of lse.  The backward reads qkv, o, dout, lse, writes exactly the B*N x 3*H*64 elements of dqkv,
+ * and reads and writes only the first vs_attn_bwd_workspace_bytes() of workspace: VS_BF16 two f32 arrays
+ * [B*H][Npad], Npad = N rounded up to 64: -lse * log2 e, then -rowsum(dO * O), their padding set to
+ * (-inf, 0); VS_F32 one array delta [B, H, N].  Neither touches a pad column, a row outside 0 .. B*N-1
+ * or memory beyond those extents, and no result depends on what such memory holds.
  * ------------------------------------------------------------------------------------------ */
 int vs_attn_fwd(int32_t dtype, int64_t B, int64_t N, int64_t H, int64_t Dh, const void* qkv,
                 int64_t ld_qkv, void* o, int64_t ld_o, float* lse, float scale, void* stream);

@@ -1930,7 +1930,9 @@ extern "C" int vs_attn_fwd(int32_t dtype, int64_t B, int64_t N, int64_t H, int64
   const double es = dtype == VS_BF16 ? 2.0 : 4.0;
   ScopedTimer timer(VS_TIMER_ATTN_FWD, s, (double)(B * N * H * 64) * 4.0 * es + (double)(B * H * N) * 4.0);
   if (dtype == VS_BF16) {
-    VS_REQUIRE(ld_qkv % 8 == 0 && ld_o % 4 == 0 && aligned16(qkv) && (((uintptr_t)o) & 7) == 0,
+    // Q rows are read and K/V tiles DMA'd as 16-byte chunks, and every forward kernel stores O rows as
+    // 16-byte vectors (the uint4 stores of the epilogues): both operands need 16-byte rows
+    VS_REQUIRE(ld_qkv % 8 == 0 && ld_o % 8 == 0 && aligned16(qkv) && aligned16(o),
                "vs_attn_fwd: bf16 rows must be 16-byte aligned");
     count_path(VS_PATH_ATTN_FWD);
     // VS_KNOB_ATTN_VARIANT low nibble: 0 the default kernel (QK(b) issued ahead of PV(a): 299 -> 252 us
