@@ -1,6 +1,8 @@
-"""Wave timeline of the bf16 attention forward from a -DVS_STAMP diagnostic build.
+"""Wave timeline of the bf16 attention forward from a -DVS_STAMP diagnostic build (the stamp buffer and
+vs_dbg_stamps live in csrc/attn_fwd.hip, the only unit that stamps).
 
-usage: VSPIKE_LIB=.../libvspike_stamp.so python scripts/stamp_attn.py
+usage: scripts/build_attn_variant.sh stamp video-spike_amd/csrc/attn_fwd.hip -DVS_STAMP
+       VSPIKE_LIB=.../libvspike_stamp.so python scripts/stamp_attn.py
 Prints the kernel span, wave lifetime percentiles, the spread of wave start times, and how many
 waves each SIMD held at once (from HW_ID: cu, simd, se, xcc).
 """

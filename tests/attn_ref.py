@@ -1,6 +1,7 @@
 """Float64 reference of the head-dim-64 attention (vs_attn_fwd / vs_attn_bwd) and a rounding model of its bf16
-kernels (csrc/attention.hip).  Pure torch on the CPU; shared by tests/test_cpu_attn_contract.py (which checks
-this module) and tests/test_gpu_attn_contract.py (which holds the kernels to it).
+kernels (csrc/attn_fwd.hip, attn_bwd.hip, attn_common.h).  Pure torch on the CPU; shared by
+tests/test_cpu_attn_contract.py (which checks this module) and tests/test_gpu_attn_contract.py (which holds the
+kernels to it).
 
 Layout (include/vspike.h): qkv [B*N, 3*H*64], Q of head h at column 64h, K at 64(H+h), V at 64(2H+h); o and dout
 [B*N, H*64]; lse [B, H, N], natural log; dqkv as qkv.
@@ -9,30 +10,30 @@ Reference: `reference()` -- softmax(Q K^T scale) V, its log-sum-exp and the clos
 
 Rounding model: `model_fwd()` / `model_bwd()` compute the same quantities in float64 except at the places where the
 bf16 kernels round to bf16, each of which can be switched off (`Rounding`).  The statements restated, by function
-in csrc/attention.hip (line numbers as of the commit that added this file):
+(forward kernels in attn_fwd.hip, backward passes in attn_bwd.hip):
 
   prescale  Q (forward, dQ pass) or K (dK/dV pass) times c = scale * log2(e), the product in f32, rounded to bf16
-            once; the scores are then in log2 units and P = exp2(S):
-              attn_fwd_bf16_kernel     `v[j] = (float)q[j] * c; qf[s] = __builtin_convertvector(v, bf16x8)`  (424-425)
-              attn_fwd16_bf16_kernel   the same statement on qf[qt][dc]                                      (855)
-              attn_bwd_dkdv_body / _pp `v[j] = (float)k[j] * c2; kf[s] = ...`                                (1215-1216, 1548)
-              attn_bwd_dq_body / _pp   `v[j] = (float)q[j] * c2; qf[s] = ...`                                (1388-1389, 1725)
-            c itself is the f32 product `scale * kLog2e` (vs_attn_fwd's launch; `c2` in the backward bodies).
+            once; the scores are then in log2 units and P = exp2(S).  One statement for every kernel:
+              attn_common.h scaled_frag  `v[j] = (float)x[j] * c; return __builtin_convertvector(v, bf16x8)`,
+              called for qf[s] (attn_fwd_bf16_kernel), qf[qt][dc] (attn_fwd16_bf16_kernel), w.kf[s] (dkdv_prologue)
+              and w.qf[s] (dq_prologue).
+            c itself is the f32 product `scale * kLog2e` (vs_attn_fwd's launch; `c2` in the backward prologues).
   p         P rounded to bf16 as the MFMA operand of O += P V and dV += P^T dO:
-              forward `pa = pack8f(p); pb = pack8f(p + 8)` (556-557), fwd16 `p[qt] = __builtin_convertvector` (997);
-              dK/dV `pb = pack8f(p)` (1308), `mma_p`'s `pack8f(pv + 8 * s2)` on P (1616, called at 1646 / 1656).
-            The forward's FAST pass also takes the row sum l from the ROUNDED P (`lacc = mfma(sel, pa, lacc)`, 559-560;
-            fwd16 `mfma16(ones, p[qt], lacc[qt])`, 1001), its SAFE pass (the redo) from the unrounded one in f32
-            (`l_half += ...`, 553 / 990) with P = exp2(S - m), m the maximum of the row's first 32-key block
-            (`m_new = move ? mxp : m_run` with first_blk, 538-543; raised later only past 2^32).  `safe` selects it.
-            dS = P * (dP - delta) uses the UNROUNDED f32 P (`ds[r] = p[r] * dpa[...]`, 1306; `pa[r] *= xa[r]`, 1664;
-            dQ: `exp2f(sacc) * dpacc`, 1470 / 1793).
+              forward `pa = pack8f(p); pb = pack8f(p + 8)` (softmax_m), fwd16 `p[qt] = __builtin_convertvector`
+              (softmax); dK/dV `pb = pack8f(p)` (attn_bwd_dkdv<false>'s slice), `mma_p`'s `pack8f(pv + 8 * s2)` on P
+              (attn_bwd_dkdv<true>).
+            The forward's FAST pass also takes the row sum l from the ROUNDED P (`lacc = mfma(sel, pa, lacc)`;
+            fwd16 `mfma16(ones, p[qt], lacc[qt])`), its SAFE pass (the redo) from the unrounded one in f32
+            (`l_half += ...`) with P = exp2(S - m), m the maximum of the row's first 32-key block
+            (`m_new = move ? mxp : m_run` with first_blk; raised later only past 2^32).  `safe` selects it.
+            dS = P * (dP - delta) uses the UNROUNDED f32 P (`ds[r] = p[r] * dpa[...]` in the 3-wave slice,
+            `pa[r] *= xa[r]` in the pair slice; dQ: `exp2f(sacc) * dpacc` in ds_mma).
   ds        dS rounded to bf16 as the operand of dK += dS^T Q and dQ += dS K:
-              `db = pack8f(ds)` (1308, 1471, 1793), `mma_p(fa, pa, dkacc)` (1665, 1668).
+              `db = pack8f(ds)` (the 3-wave dK/dV slice, ds_mma), `mma_p(fa, pa, w.dkacc)` (the pair slice).
   out       O, dQ, dK, dV rounded to bf16 at the store, after 1/l (O) or `* scale` (dQ, dK) in f32:
-              `pack4(oacc * inv ...)` (783, 1107), `pack4(dkacc * scale ...)` / `pack4(dvacc ...)` (1349-1351, 1692-1694),
-              `pack4(dqacc * scale ...)` (1503, 1857).
-  delta = rowsum(dO * O) takes O as it is given (the bf16 O of the forward, attn_rowprep_kernel 1143-1157), and lse is
+              `pack4` in fwd_o_put4 on `oacc * inv`, `pack4(dkacc * scale ...)` / `pack4(dvacc ...)` (dkdv_epilogue),
+              `pack4(dqacc * scale ...)` (dq_epilogue).
+  delta = rowsum(dO * O) takes O as it is given (the bf16 O of the forward, attn_rowprep_kernel), and lse is
   the f32 the forward stored; both are inputs of `model_bwd`.  Everything else -- the f32 MFMA accumulation, exp2,
   log2, 1/l -- is float64 here.
 """

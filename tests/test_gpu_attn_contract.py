@@ -1,4 +1,4 @@
-"""The contract of the head-dim-64 attention entries vs_attn_fwd / vs_attn_bwd (csrc/attention.hip), at op level.
+"""The contract of the head-dim-64 attention entries vs_attn_fwd / vs_attn_bwd (csrc/attn_fwd.hip, attn_bwd.hip), at op level.
 
 Reference and bars.  tests/attn_ref.py holds the float64 reference and a rounding model of the bf16 kernels (the
 same float64 arithmetic with the kernels' documented bf16 roundings); tests/test_cpu_attn_contract.py checks both

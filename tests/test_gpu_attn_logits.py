@@ -1,6 +1,6 @@
 """The attention forward's fast pass at trained-model logit scales.
 
-The bf16 forward (csrc/attention.hip attn_fwd_bf16_kernel) computes p = exp2(s) with NO running row
+The bf16 forward (csrc/attn_fwd.hip attn_fwd_bf16_kernel) computes p = exp2(s) with NO running row
 maximum and checks at the end that every query's row sum stayed within [2^-100, 2^96]; a workgroup
 with a query outside that band re-runs its tile under the safe online softmax.  Random-init weights
 give small scores, so the benchmark never takes the re-run; a trained ViT (the reference loads
