@@ -983,8 +983,9 @@ int vs_g256_scratch_free(void);
 #define VS_KNOB_G256_DBG    30   /* VS_DEBUG_KNOBS builds only: 256 x 256 GEMM bit 0 = no operand DMA, bit 1 = no epilogue stores (WRONG results) */
 #define VS_KNOB_NO_DW256    31   /* 1: the long-K dW products on the split-K dW kernel instead of the 256 x 256 persistent one */
 #define VS_KNOB_G256_STAGGER 32  /* 256 x 256 GEMM: odd-slot workgroups start N x s_sleep(127) (~4 us) late */
-#define VS_KNOB_CONV_DW128  33   /* 1: Conv3d weight gradient on 128-wide k tiles where K >= 128 (measured slower than the 64-wide default) */
-#define VS_KNOB_CONV_MFMA   34   /* Conv3d weight gradient's f32 MFMA shape: 0 = 16x16x4 (default), 1 = 32x32x2 (measured slower) */
+/* ids 33 (conv_dw128: Conv3d weight gradient on 128-wide k tiles) and 34 (conv_mfma: its 32x32x2 MFMA form), both
+   measured slower than the one schedule kept, are retired since ABI v16: they read 0 and setting them
+   does nothing */
 #define VS_KNOB_DW256_ALL   36   /* 1: the 768 x 768 projection dW on the 256 x 256 dW kernel too (default: split-K dW tiles) */
 #define VS_KNOB_LN_FWD_BLOCKS 37 /* LayerNorm forward (vectorised) grid cap (0 = default 768) */
 #define VS_KNOB_G256_A3     35   /* 256 x 256 forward / dX GEMM: the streamed A operand in three LDS slots (DMA two stages ahead, counted stage wait): 0 / 1 = on (default), 2 = off (two slots, round 5) */

@@ -3,7 +3,8 @@
 (fwd + bwd + AdamW) after its own re-warm step, plus the per-class kernel times of one instrumented
 step per variant (conv fwd / dX / dW, BN).
 
-usage: python scripts/r3d_ab.py --knob conv_mfma --values 1,2 [--batch 16 --rounds 5 --steps 5]
+usage: python scripts/r3d_ab.py --knob NAME --values 0,1 [--batch 16 --rounds 5 --steps 5]
+(NAME: one of vspike._lib.KNOB_NAMES)
 """
 import argparse
 import json
@@ -23,7 +24,7 @@ import bench  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--knob", default="conv_mfma")
+    ap.add_argument("--knob", required=True)
     ap.add_argument("--values", default="1,2")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=5)

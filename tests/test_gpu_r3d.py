@@ -1,4 +1,5 @@
-"""BASELINE C4: the R3D-18 encoder (csrc/conv3d.hip, vspike/r3d.py) against the CPU oracle's torch
+"""BASELINE C4: the R3D-18 encoder (csrc/conv_igemm.hip, conv_dw.hip, bn3d.hip with conv_common.h;
+vspike/r3d.py) against the CPU oracle's torch
 restatement (oracle/cpu_ref.py r3d18_forward: F.conv3d / F.batch_norm / F.relu on NCDHW tensors).
 
 PARITY UNPINNED: the reference has no CNN encoder, so no reference output
@@ -61,7 +62,9 @@ def _spec(ci, co, k, s, p):
 
 # (N, D, H, W, Ci, Co, k, s, p): the stem, the stride-1 3x3x3 body conv, the stride-2 first convs of
 # stages 2-4, the 1x1x1 stride-2 shortcut, odd extents (tails of the 128-row tiles, parity classes of
-# unequal size)
+# unequal size); the last two have fewer than 32 output voxels per clip (24 and 6), so the clip digit of
+# the weight gradient's 32-row step is 1 and 5 (0 in every case above) and the gather's incremental
+# advance steps the clip index itself (the second with carries in W and H)
 CONV_CASES = [
     (2, 8, 20, 20, 4, 64, (3, 7, 7), (1, 2, 2), (1, 3, 3)),
     (2, 6, 14, 14, 64, 64, (3, 3, 3), (1, 1, 1), (1, 1, 1)),
@@ -69,13 +72,15 @@ CONV_CASES = [
     (1, 5, 9, 7, 128, 256, (3, 3, 3), (2, 2, 2), (1, 1, 1)),
     (2, 6, 14, 14, 64, 128, (1, 1, 1), (2, 2, 2), (0, 0, 0)),
     (1, 3, 5, 5, 256, 64, (3, 3, 3), (1, 1, 1), (1, 1, 1)),
+    (4, 2, 3, 4, 64, 64, (3, 3, 3), (1, 1, 1), (1, 1, 1)),
+    (12, 1, 2, 3, 64, 64, (1, 3, 3), (1, 1, 1), (0, 1, 1)),
 ]
 
 
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv3d_fwd_dx_dw_match_torch(case):
     """vs_conv3d_fwd / _dx / _dw against torch's conv3d and its autograd (fp64 on the CPU) on the same
-    f32 inputs; dX both overwriting and accumulating; the fused BatchNorm statistics partials."""
+    f32 inputs; dX and dW both overwriting and accumulating; the fused BatchNorm statistics partials."""
     from vspike import r3d, _lib as L
     N, D, H, W, Ci, Co, k, s, p = case
     g = torch.Generator().manual_seed(sum(case[:6]))
@@ -109,6 +114,10 @@ def test_conv3d_fwd_dx_dw_match_torch(case):
     assert float(((st[:, 0] - s_ref).abs() / tabs).max()) < 1e-5
     assert _maxrel(st[:, 1], m2_ref) < 1e-5
     assert _maxrel(dw, rdw.permute(0, 2, 3, 4, 1)) < 1e-5
+    base = torch.randn(w_dev.shape, generator=g).to(DEV)
+    dw3 = base.clone()
+    r3d.conv3d_dw(d, x_dev, gy_dev, dw3, accumulate=True)
+    assert _maxrel(dw3, rdw.permute(0, 2, 3, 4, 1) + base.double().cpu()) < 1e-5
     if Ci % 64 == 0:
         dx = torch.full((N, D, H, W, Ci), float("nan"), device=DEV)      # every element must be written
         r3d.conv3d_dx(d, gy_dev, w_dev, dx)

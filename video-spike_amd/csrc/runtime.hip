@@ -33,8 +33,9 @@ static const KnobDef kKnobs[VS_KNOB_COUNT] = {
     {"VSPIKE_NO_FULLK", 0},    {"VSPIKE_NO_RING", 0},      {"VSPIKE_NO_LNF_FUSE", 0},  {"VSPIKE_NO_LN_FUSE", 0},
     {"VSPIKE_DW_BM", 0},       {"VSPIKE_DW_BN", 0},        {"VSPIKE_DW_SPLITS", 0},    {"VSPIKE_DW_STAGES", 0},
     {"VSPIKE_LN_BLOCKS", 0},   {"VSPIKE_DH_F32", 0},       {"VSPIKE_NO_PATCH_FUSED", 0}, {"VSPIKE_NO_DW_GROUP", 0},
-    {"VSPIKE_ATTN_VARIANT", 0}, {"VSPIKE_SLAB_WV", 0}, {"VSPIKE_WRES_WV", 0}, {"VSPIKE_WRES_DBG", 0}, {"VSPIKE_G256", 0}, {"VSPIKE_G256_GRID", 0}, {"VSPIKE_G256_DBG", 0}, {"VSPIKE_NO_DW256", 0}, {"VSPIKE_G256_STAGGER", 0}, {"VSPIKE_CONV_DW128", 0},
-    {"VSPIKE_CONV_MFMA", 0}, {"VSPIKE_G256_A3", 0}, {"VSPIKE_DW256_ALL", 0}, {"VSPIKE_LN_FWD_BLOCKS", 0}};
+    {"VSPIKE_ATTN_VARIANT", 0}, {"VSPIKE_SLAB_WV", 0}, {"VSPIKE_WRES_WV", 0}, {"VSPIKE_WRES_DBG", 0}, {"VSPIKE_G256", 0}, {"VSPIKE_G256_GRID", 0}, {"VSPIKE_G256_DBG", 0}, {"VSPIKE_NO_DW256", 0}, {"VSPIKE_G256_STAGGER", 0},
+    {nullptr, 0}, {nullptr, 0},   // ids 33, 34: retired (vspike.h)
+    {"VSPIKE_G256_A3", 0}, {"VSPIKE_DW256_ALL", 0}, {"VSPIKE_LN_FWD_BLOCKS", 0}};
 static std::atomic<int> g_knob[VS_KNOB_COUNT];
 static std::once_flag g_knob_once;
 static void knob_init() {
@@ -109,7 +110,8 @@ ScopedTimer::~ScopedTimer() {
 // 11: vs_contrast_frames (csrc/contrast_loader.hip)
 // 12: vs_rrr_pixel_* (csrc/rrr_pixel.hip) and vs_rrr_pixel_dispatch_counts
 // 13: vs_flow_median2, vs_flow_quantiles, vs_flow_clip_mean, vs_motion_energy, vs_flow_plan (csrc/flow_features.hip)
-extern "C" int vs_version(void) { return 15; }
+// 14: knob id 38 retired; 16: knob ids 33, 34 (the Conv3d weight gradient's losing variants) retired
+extern "C" int vs_version(void) { return 16; }
 extern "C" const char* vs_build_id(void) { return VS_BUILD_ID; }
 
 extern "C" int vs_knob_get(int k) {
